@@ -13,6 +13,15 @@ seq range (weak scaling); the only collective is an RCCL all-reduce of the
 per-rank counters {records, payload bytes, auth failures} and the timing max.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--len L]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (the
+per-kernel and roofline figures in it come from HIP events recorded in the
+timed steps themselves).  ``--full`` adds what takes runs of its own: the
+untimed correctness checks (every record authentic in the last step, a fresh
+round trip per cipher, sampled records against the C oracle; exit 3 on a
+failure) and the CPU baselines.  ``--dump-outputs DIR`` writes what the last
+timed step computed as DIR/<name>.npy (DumpSample below).
 """
 import argparse
 import json
@@ -286,6 +295,91 @@ def check_world(gpus, env=None):
     return None
 
 
+def headline_keys(torch):
+    """The headline's fixed IV and session keys (host generator, seed 0x7716):
+    (iv, {alg: key}), the same in every run and on every rank."""
+    hrng = torch.Generator().manual_seed(0x7716)
+    iv = bytes(torch.randint(0, 256, (12,), dtype=torch.uint8, generator=hrng).tolist())
+    keys = {"aes128gcm": bytes(torch.randint(0, 256, (16,), dtype=torch.uint8, generator=hrng).tolist()),
+            "chacha20-poly1305": bytes(torch.randint(0, 256, (32,), dtype=torch.uint8,
+                                                     generator=hrng).tolist())}
+    return iv, keys
+
+
+DUMP_RECORDS = 128            # sampled records per dumped payload array
+DUMP_STATUS_MAX = 1 << 20     # status entries dumped per cipher
+DUMP_SEED = 0xd0c5
+
+
+def dump_pick(n, count, seed=DUMP_SEED):
+    """At most ``count`` >= 2 record indices of a batch of n (all of them
+    when n is no larger): the first, the last and count - 2 seeded random
+    ones, ascending, without repeats.  The same (n, count) gives the same
+    indices in every run."""
+    import numpy as np
+    if count >= n:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    others = rng.choice(n, count - 2, replace=False)
+    return np.unique(np.concatenate([[0, n - 1], others])).astype(np.int64)
+
+
+class DumpSample(object):
+    """--dump-outputs: what a caller of the timed path receives from the last
+    timed step, as float32 .npy files (one value per byte), rank 0's shard:
+
+      <alg>_sealed.npy   (k, L + 16)  ct || tag of the sampled records
+      <alg>_opened.npy   (k, L)       the plaintext open wrote back for them
+      <alg>_status.npy   (m,)         open's per-record verdict (1 = authentic)
+      record_index.npy   (k,)         the sampled records (dump_pick: first,
+                                      last, seeded others), float64
+      status_index.npy   (m,)         the records of the status arrays, float64;
+                                      only above 2^20 records per GPU (up to
+                                      there the status arrays hold every record)
+
+    for alg in aes128gcm, chacha20-poly1305.  The whole outputs are 4 x 16 GiB
+    at the headline shape, so k <= 128 records are kept (under 64 MB in all).
+    Both AEADs write the same payload buffers, so grab() copies the sampled
+    rows aside on the launch stream right behind each launch of the last
+    step: one small gather per launch, outside the per-kernel event pairs."""
+
+    def __init__(self, torch, n, L, SL, dev):
+        self.torch, self.n, self.L, self.SL = torch, n, L, SL
+        k = max(1, min(n, DUMP_RECORDS, 48000000 // (16 * (L + TAG_LEN))))
+        self.idx = dump_pick(n, k)
+        self.d_idx = torch.from_numpy(self.idx).to(dev)
+        self.st_idx = dump_pick(n, DUMP_STATUS_MAX, DUMP_SEED + 1)
+        self.snap = {}
+        for a in ("aes128gcm", "chacha20-poly1305"):
+            self.snap[(a, "seal")] = torch.empty((len(self.idx), SL), dtype=torch.uint8, device=dev)
+            self.snap[(a, "open")] = torch.empty((len(self.idx), L), dtype=torch.uint8, device=dev)
+        self.written = None
+
+    def grab(self, alg, op, buf):
+        rows = buf.view(self.n, self.SL if op == "seal" else self.L)
+        self.torch.index_select(rows, 0, self.d_idx, out=self.snap[(alg, op)])
+
+    def write(self, path, status):
+        import numpy as np
+        os.makedirs(path, exist_ok=True)
+        out = {"record_index": self.idx.astype(np.float64)}
+        if len(self.st_idx) < self.n:
+            out["status_index"] = self.st_idx.astype(np.float64)
+        st_idx = self.torch.from_numpy(self.st_idx)
+        for (a, op), t in self.snap.items():
+            # the bytes between L + 16 and the sealed stride are never written
+            width = self.L + TAG_LEN if op == "seal" else self.L
+            out["%s_%s" % (a, "sealed" if op == "seal" else "opened")] = \
+                t[:, :width].cpu().numpy().astype(np.float32)
+        for a, s in status.items():
+            out["%s_status" % a] = s.cpu()[st_idx].numpy().astype(np.float32)
+        for name, arr in out.items():
+            np.save(os.path.join(path, name + ".npy"), arr)
+        self.written = {"dir": path, "records": len(self.idx),
+                        "arrays": {name: list(arr.shape) for name, arr in sorted(out.items())},
+                        "bytes": int(sum(arr.nbytes for arr in out.values()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -298,6 +392,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="CPU baseline: seconds each process seals/opens")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="headline: after the timed steps also run the untimed correctness checks "
+                         "(round trips, C oracle samples; exit 3 on a failure) and, unless "
+                         "--no-cpu-baseline, the CPU baselines.  Off by default: a plain run only "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline: write what the last timed step computed to DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the records, see DumpSample)")
     ap.add_argument("--e2e", action="store_true", help="also time the host<->device path")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "r06", "traffic.json"),
                     help="per-launch HBM bytes from tools/traffic.sh (rocprofv3 FETCH_SIZE / "
@@ -332,6 +434,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.config != "headline":
+        ap.error("--dump-outputs writes the headline's outputs (--config headline)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # N ranks, one process per GPU, started here before anything in this
         # process touches the GPU; this process only waits and passes on the
@@ -391,11 +497,7 @@ def main():
     back = torch.empty(n * L, dtype=torch.uint8, device=dev)
     nonces = torch.empty(NONCE_LEN * n, dtype=torch.uint8, device=dev)
     aad = torch.tensor(list(tls13_aad(L)), dtype=torch.uint8, device=dev)
-    hrng = torch.Generator().manual_seed(0x7716)
-    iv = bytes(torch.randint(0, 256, (12,), dtype=torch.uint8, generator=hrng).tolist())
-    keys = {"aes128gcm": bytes(torch.randint(0, 256, (16,), dtype=torch.uint8, generator=hrng).tolist()),
-            "chacha20-poly1305": bytes(torch.randint(0, 256, (32,), dtype=torch.uint8,
-                                                     generator=hrng).tolist())}
+    iv, keys = headline_keys(torch)
     ciphers = {"aes128gcm": tlsgpu.HipAESGCM(bytearray(keys["aes128gcm"])),
                "chacha20-poly1305": tlsgpu.HipCHACHA20_POLY1305(bytearray(keys["chacha20-poly1305"]))}
     tgd.shard_nonces(tlsgpu, iv, first, n, nonces)
@@ -410,8 +512,12 @@ def main():
     stream = torch.cuda.current_stream()
     kinds = [(a, op) for a in ciphers for op in ("seal", "open")]
     ev = {k: [] for k in kinds}
+    # --dump-outputs: the sampled records of each launch's output are copied
+    # aside in the last timed step, right behind the launch (the payload
+    # buffers are shared, so the next launch overwrites them)
+    dump = DumpSample(torch, n, L, SL, dev) if args.dump_outputs and rank == 0 else None
 
-    def step(record):
+    def step(record, last=False):
         for a, c in ciphers.items():
             for op, fn, b in (("seal", tlsgpu.seal_batch, seal_b), ("open", tlsgpu.open_batch, open_b[a])):
                 if record:
@@ -422,39 +528,48 @@ def main():
                 if record:
                     e1.record(stream)
                     ev[(a, op)].append((e0, e1))
+                if last and dump is not None:
+                    dump.grab(a, op, sealed if op == "seal" else back)
 
     for _ in range(args.warmup):
         step(False)
-    elapsed = tgd.timed(torch, dist, world, lambda s: step(True), args.steps)
+    elapsed = tgd.timed(torch, dist, world, lambda s: step(True, s == args.steps - 1), args.steps)
+    if dump is not None:
+        dump.write(args.dump_outputs, status)
 
-    # correctness of the timed work (untimed): every record of both AEADs
-    # authentic in the last step, then per cipher a fresh seal -> open round
-    # trip (the shared payload buffers hold only the last cipher's output)
-    fails = {a: n - int(status[a].sum().item()) for a in ciphers}
-    samples, verified = [], {}
-    pick = sorted(set([0, n - 1, n // 2, (n * 7) // 11]))
-    for a, c in ciphers.items():
-        status[a].zero_()
-        back.zero_()
-        tlsgpu.seal_batch(c, seal_b, stream)
-        tlsgpu.open_batch(c, open_b[a], stream)
-        torch.cuda.synchronize()
-        verified[a] = int(status[a].sum().item()) == n and bool(torch.equal(back, inp))
-        for i in pick:   # for the CPU leg's re-check
-            samples.append((a, keys[a], tgd.tls13_nonces(iv, first + i, 1),
-                            inp[i * L:(i + 1) * L].cpu().numpy().tobytes(), bytes(tls13_aad(L)),
-                            sealed[i * SL:i * SL + L + TAG_LEN].cpu().numpy().tobytes()))
-    # every rank checks its own sampled records against the C oracle, and the
-    # line's verdict is reduced over all ranks (a wrong seq offset on rank g
-    # is symmetric in seal and open, so only the oracle sees it)
-    samples = corrupt_for_test(samples, rank, 5)
-    bad = headline_check(samples)
-    ok, bad_all, checked_all = verify_shards(torch, dist, all(verified.values()), bad, len(samples), device=dev)
+    fails, samples, verified = None, [], None
+    ok, bad_all, checked_all = True, None, None
+    if args.full:
+        # correctness of the timed work (untimed): every record of both AEADs
+        # authentic in the last step, then per cipher a fresh seal -> open round
+        # trip (the shared payload buffers hold only the last cipher's output)
+        fails = {a: n - int(status[a].sum().item()) for a in ciphers}
+        verified = {}
+        pick = sorted(set([0, n - 1, n // 2, (n * 7) // 11]))
+        for a, c in ciphers.items():
+            status[a].zero_()
+            back.zero_()
+            tlsgpu.seal_batch(c, seal_b, stream)
+            tlsgpu.open_batch(c, open_b[a], stream)
+            torch.cuda.synchronize()
+            verified[a] = int(status[a].sum().item()) == n and bool(torch.equal(back, inp))
+            for i in pick:   # for the CPU leg's re-check
+                samples.append((a, keys[a], tgd.tls13_nonces(iv, first + i, 1),
+                                inp[i * L:(i + 1) * L].cpu().numpy().tobytes(), bytes(tls13_aad(L)),
+                                sealed[i * SL:i * SL + L + TAG_LEN].cpu().numpy().tobytes()))
+        # every rank checks its own sampled records against the C oracle, and the
+        # line's verdict is reduced over all ranks (a wrong seq offset on rank g
+        # is symmetric in seal and open, so only the oracle sees it)
+        samples = corrupt_for_test(samples, rank, 5)
+        bad = headline_check(samples)
+        ok, bad_all, checked_all = verify_shards(torch, dist, all(verified.values()), bad, len(samples),
+                                                 device=dev)
     # the only collectives: counters summed, the timed span max-reduced and
     # the per-rank kernel times gathered (RCCL)
     sums, elapsed = tgd.reduce_counters(torch, dist, [n * args.steps * len(kinds),
                                                       n * L * args.steps * len(kinds),
-                                                      sum(fails.values())], elapsed, device=dev)
+                                                      sum(fails.values()) if fails else 0],
+                                         elapsed, device=dev)
     payload_bytes = sums[1]
     per_kernel, my_ms = {}, []
     for (a, op), lst in ev.items():
@@ -507,14 +622,18 @@ def main():
                          "bytes_per_record": algorithmic_bytes(1, L, dom_op),
                          "read_bytes_per_record": read_bytes(1, L, dom_op),
                          "algorithmic_bytes_per_launch": algorithmic_bytes(n, L, dom_op)},
-            "verified": bool(ok),
-            "verified_scope": "all %d rank(s): MIN of each rank's round trip and oracle agreement" % world,
+            "full": bool(args.full),
+            "verified": bool(ok) if args.full else None,
+            "verified_scope": ("all %d rank(s): MIN of each rank's round trip and oracle agreement" % world
+                               if args.full else "not checked (a plain run; --full checks)"),
             "verified_per_cipher_rank0": verified,
             "oracle_checked_records": checked_all, "oracle_mismatches": bad_all,
-            "auth_failures": int(sums[2]),
+            "auth_failures": int(sums[2]) if args.full else None,
             "auth_failures_per_cipher": fails,
             "dist_backend": dist.get_backend() if tgd.group_active(dist) else None,
         }
+        if dump is not None:
+            line["dumped_outputs"] = dump.written
         if dist_info:
             line["dist_selftest"] = dist_info
         if world > 1:
@@ -525,7 +644,7 @@ def main():
                                  for nm, ms in zip(names, r)} for r in rows]
         if e2e:
             line["end_to_end"] = e2e
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, after the collectives, at any N (the other ranks
             # go on to tear down their process group)
             cores = args.cpu_cores or host_cores()[0]

@@ -43,8 +43,11 @@ def _run(args, env_extra=None, timeout=240):
 
 
 def test_gpus_2_starts_two_ranks():
+    # the launcher stops the other rank as soon as it sees one fail, and it
+    # looks every 0.1 s by default: a rank a little behind the first was killed
+    # before it got to print.  Its first look 5 s in finds both ranks done.
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--records", "64",
-              "--no-cpu-baseline"], {"TLSGPU_DIST_BACKEND": "gloo"})
+              "--no-cpu-baseline"], {"TLSGPU_DIST_BACKEND": "gloo", "PET_MONITOR_INTERVAL": "5"})
     assert r.returncode != 0
     out = r.stdout + r.stderr
     # both ranks reached init_process (no GPU here) under the launcher
@@ -71,6 +74,25 @@ def test_nccl_needs_a_gpu_per_rank():
 def test_single_gpu_configs_refuse_n(config):
     r = _run(["--gpus", "2", "--config", config])
     assert r.returncode == 2 and "runs on one GPU" in r.stderr
+
+
+def test_dump_options_refused_where_they_do_not_apply():
+    r = _run(["--config", "c4", "--dump-outputs", "unused"])
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_pick_is_fixed():
+    """The records --dump-outputs samples: the same for the same batch, the
+    first and the last among them, ascending without repeats; every record
+    of a batch no larger than the sample."""
+    import bench
+    a, b = bench.dump_pick(1 << 20, 128), bench.dump_pick(1 << 20, 128)
+    assert a.tolist() == b.tolist() and 126 <= len(a) <= 128
+    assert a[0] == 0 and a[-1] == (1 << 20) - 1 and all(x < y for x, y in zip(a, a[1:]))
+    assert bench.dump_pick(100, 128).tolist() == list(range(100))
+    assert bench.dump_pick(128, 128).tolist() == list(range(128))
 
 
 def test_cpu_config1_in_full_matches_reference_digest():

@@ -12,7 +12,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 400 --timeou
 tail -3 $O/pytest.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
-CB=--no-cpu-baseline; [ "$CPU" = 1 ] && CB=
+CB="--full --no-cpu-baseline"; [ "$CPU" = 1 ] && CB=--full
 timeout -k 10 600 python -u bench.py $CB > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
 cd /tmp && export TMPDIR=/tmp

@@ -6,7 +6,7 @@
 set -e
 O=gpurun_out/$1; mkdir -p $O
 TLSGPU_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 2 --warmup 1 --records 65536 \
-  --no-cpu-baseline > $O/bench2_gloo.json 2> $O/bench2_gloo.err
+  --full --no-cpu-baseline > $O/bench2_gloo.json 2> $O/bench2_gloo.err
 cat $O/bench2_gloo.json
 rc=0
 timeout -k 10 300 python bench.py --gpus 2 --steps 2 --warmup 1 --records 65536 --no-cpu-baseline \

@@ -5,8 +5,8 @@
 # steps:
 #   tests[=EXPR]   pytest -m gpu (-k EXPR)            -> pytest.log
 #   smoke          __graft_entry__.smoke()             -> smoke.log
-#   bench          bench.py (headline, CPU baseline)   -> bench.json
-#   bench-nocpu    bench.py --no-cpu-baseline          -> bench.json
+#   bench          bench.py --full (headline, checks, CPU baseline) -> bench.json
+#   bench-nocpu    bench.py --full --no-cpu-baseline (headline, checks) -> bench.json
 #   c4 | c5 | ccm | c1 | e2e | ingest                  -> bench_<step>.json
 #   distself       bench.py --dist-selftest: RCCL at world size 1 -> bench_dist_selftest.json
 #   n2             bench.py --gpus 2 --config c5 --records 65536 over gloo on
@@ -49,21 +49,21 @@ for st0 in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err; cat $O/bench.json ;;
+      timeout -k 10 600 python -u bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err; cat $O/bench.json ;;
     bench-nocpu)
-      timeout -k 10 600 python -u bench.py --no-cpu-baseline $BENCH_ARGS > $O/bench.json 2> $O/bench.err; cat $O/bench.json ;;
+      timeout -k 10 600 python -u bench.py --full --no-cpu-baseline $BENCH_ARGS > $O/bench.json 2> $O/bench.err; cat $O/bench.json ;;
     c4|c5|ccm|c1|ingest)
       timeout -k 10 600 python -u bench.py --config $st $BENCH_ARGS > $O/bench_$st$SUF.json 2> $O/bench_$st$SUF.err
       cat $O/bench_$st$SUF.json ;;
     distself)
-      timeout -k 10 600 python -u bench.py --dist-selftest --no-cpu-baseline $BENCH_ARGS > $O/bench_dist_selftest.json 2> $O/bench_dist_selftest.err
+      timeout -k 10 600 python -u bench.py --dist-selftest --full --no-cpu-baseline $BENCH_ARGS > $O/bench_dist_selftest.json 2> $O/bench_dist_selftest.err
       cat $O/bench_dist_selftest.json ;;
     e2e)
       timeout -k 10 600 python -u bench.py --e2e --no-cpu-baseline $BENCH_ARGS > $O/bench_e2e.json 2> $O/bench_e2e.err; cat $O/bench_e2e.json ;;
     n2)
       TLSGPU_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --config c5 --records 65536 \
         --steps 3 --warmup 1 > $O/bench_n2_c5.json 2> $O/bench_n2_c5.err; cat $O/bench_n2_c5.json
-      TLSGPU_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --records 65536 \
+      TLSGPU_DIST_BACKEND=gloo timeout -k 10 400 python -u bench.py --gpus 2 --records 65536 --full \
         --steps 3 --warmup 1 > $O/bench_n2.json 2> $O/bench_n2.err; cat $O/bench_n2.json ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
