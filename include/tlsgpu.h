@@ -233,6 +233,67 @@ typedef struct tg_records {
 int tg_seal_records(tg_key* k, const tg_records* r, void* stream);
 int tg_open_records(tg_key* k, const tg_records* r, void* stream);
 
+/* Record framing for MANY sessions in one batch: the pending records of many
+ * RecordLayers (one direction each) through one call.  Record i belongs to
+ * session s = session[i]; it is sealed / opened under key-table entry s with
+ * the fixed IV in row s of iv_table and a per-session sequence number.  The
+ * nonce, AAD, header, explicit-nonce, TLS 1.3 inner-plaintext, limit and
+ * de-padding rules, and the data / wire arrays, are those of tg_records; one
+ * TLS version and one algorithm (the key handle's) per batch.  All arrays
+ * are DEVICE pointers.
+ *   nsessions  must equal the key handle's nkeys (a single-key handle with
+ *              nsessions == 1 is valid).
+ *   iv_table   nsessions rows of fixed_iv_len bytes, packed -- the layout
+ *              tg_hkdf_expand_label writes for the "iv" label.
+ *   Exactly one of seq / seq_next is given (anything else is TG_EINVAL):
+ *   seq        explicit mode: record i has sequence number seq[i].
+ *   seq_next   counter mode: nsessions counters, one per session (a
+ *              RecordLayer's _writeState.seqnum / _readState.seqnum).  Record
+ *              i gets seq_next[s] as it was before the call plus the number
+ *              of earlier records j < i of this batch with session[j] == s;
+ *              after the call seq_next[s] has advanced by the session's
+ *              record count (sessions without records are untouched).  The
+ *              assignment follows batch order and is deterministic.  On open
+ *              every record of a session consumes a number whatever its
+ *              status, as getSeqNumBytes() at the top of _decryptAndUnseal
+ *              (recordlayer.py:782).  The numbers come from a stable sort
+ *              of the batch by session (one algorithm, and no kernel with a
+ *              private segment, at every n).
+ *   seq_out    optional, n entries: the number record i was given, in either
+ *              mode (not written for a skipped record).
+ * A record with session[i] >= nsessions is skipped: nothing is read past
+ * either table and no sequence number is consumed; seal writes nothing to
+ * wire and sets wire_len[i] = 0; open sets status[i] = TG_REC_BAD_SESSION,
+ * data_len[i] = 0 and ctype[i] = 0 and writes nothing to data.
+ * n is at most 2^32 - 2 in either mode; a larger n is TG_EINVAL before anything
+ * is launched.  Two calls that share seq_next must be ordered on one stream. */
+#define TG_REC_BAD_SESSION 8    /* session[i] >= nsessions: record skipped */
+
+typedef struct tg_session_records {
+    uint64_t n;
+    uint32_t version;           /* TG_TLS12 or TG_TLS13, one per batch */
+    uint32_t fixed_iv_len;      /* 4 or 12, one per batch: the rule of tg_records */
+    uint32_t recv_limit;        /* open: recv_record_limit (0 = 2^14) */
+    uint64_t nsessions;
+    const uint8_t* iv_table;
+    const uint32_t* session;
+    const uint64_t* seq;
+    uint64_t* seq_next;
+    uint64_t* seq_out;
+    uint8_t* data;
+    const uint64_t* data_off;
+    uint32_t* data_len;
+    uint8_t* ctype;
+    const uint32_t* pad_len;    /* seal, TLS 1.3 only; NULL = no padding */
+    uint8_t* wire;
+    const uint64_t* wire_off;
+    uint32_t* wire_len;
+    uint8_t* status;            /* open */
+} tg_session_records;
+
+int tg_seal_session_records(tg_key* k, const tg_session_records* r, void* stream);
+int tg_open_session_records(tg_key* k, const tg_session_records* r, void* stream);
+
 /* Bulk TLS 1.3 key setup on the device -- the
  * per-session work of RecordLayer.calcTLS1_3PendingState
  * (recordlayer.py:1268-1323) and _calcTLS1_3KeyUpdate (:1325-1350) for many

@@ -398,7 +398,7 @@ struct ScratchAlloc {
 
 int records_scratch(uint64_t n, hipStream_t st, ScratchAlloc& a, tg::RecScratch& s) {
     const size_t per = 8 + 8 + 4 + 12 + 16 + 4 + 1 + 1;
-    const size_t bytes = per * n + 64 + 64;
+    const size_t bytes = per * n + 64 + 64 + 64;
     a.s = st;
     if (tg::stream_alloc(&a.base, bytes, st)) return fail(TG_EHIP, "scratch allocation failed");
     uint8_t* p = static_cast<uint8_t*>(a.base);
@@ -412,33 +412,57 @@ int records_scratch(uint64_t n, hipStream_t st, ScratchAlloc& a, tg::RecScratch&
     s.aead_st = p; p += n;
     p = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(p) + 63) & ~uintptr_t(63));
     s.dummy = p;
+    s.sink = p + 64;
     HIP_TRY(hipMemsetAsync(s.dummy, 0, 32, st));
     return TG_OK;
+}
+
+// _getNonce (recordlayer.py:522-534) then asserts a 12-byte nonce (:556):
+// TLS 1.3 XORs a 12-byte IV; TLS 1.2 AES-GCM / AES-CCM append the 8-byte
+// sequence number to a 4-byte IV; TLS 1.2 ChaCha XORs a 12-byte IV (RFC
+// 7905) or appends to a 4-byte one (draft-00).
+int check_framing(const tg_key* k, uint32_t version, uint32_t ivl) {
+    if (version != TG_TLS12 && version != TG_TLS13)
+        return fail(TG_EINVAL, "version must be TG_TLS12 or TG_TLS13");
+    const bool chacha = k->alg == TG_CHACHA20_POLY1305;
+    const bool ok = version == TG_TLS13 ? ivl == 12 : chacha ? (ivl == 12 || ivl == 4) : ivl == 4;
+    if (!ok)
+        return fail(TG_EINVAL, "fixed IV of %u bytes gives no 12-byte nonce for this suite "
+                    "(TLS 1.3: 12; TLS 1.2 AES: 4; TLS 1.2 ChaCha: 12 or 4)", ivl);
+    return TG_OK;
+}
+
+// The AEAD batch between the framing kernels: payloads, nonces and AAD rows
+// as the prep kernel laid them out.
+void framing_batch(tg_batch& b, uint64_t n, const tg::RecScratch& s, bool seal, const uint8_t* data,
+                   const uint64_t* data_off) {
+    memset(&b, 0, sizeof(b));
+    b.n = n;
+    b.len = s.len;
+    b.nonce = s.nonce;
+    b.aad = s.aad;
+    b.aad_stride = 16;
+    b.aad_len = s.aad_len;
+    b.out_off = s.out_abs;          // absolute addresses: out base NULL
+    if (seal) {
+        b.in = data;
+        b.in_off = data_off;
+    } else {
+        b.in_off = s.in_abs;
+        b.status = s.aead_st;
+    }
 }
 
 int records(tg_key* k, const tg_records* r, void* stream, bool seal) {
     if (!k || !r) return fail(TG_EINVAL, "null argument");
     if (r->n == 0) return TG_OK;
     if (k->nkeys != 1) return fail(TG_EINVAL, "record framing needs a single-key handle");
-    if (r->version != TG_TLS12 && r->version != TG_TLS13)
-        return fail(TG_EINVAL, "version must be TG_TLS12 or TG_TLS13");
-    // _getNonce (recordlayer.py:522-534) then asserts a 12-byte nonce (:556):
-    // TLS 1.3 XORs a 12-byte IV; TLS 1.2 AES-GCM / AES-CCM append the 8-byte
-    // sequence number to a 4-byte IV; TLS 1.2 ChaCha XORs a 12-byte IV (RFC
-    // 7905) or appends to a 4-byte one (draft-00).
-    {
-        const bool chacha = k->alg == TG_CHACHA20_POLY1305;
-        const uint32_t ivl = r->fixed_iv_len;
-        const bool ok = r->version == TG_TLS13 ? ivl == 12 : chacha ? (ivl == 12 || ivl == 4) : ivl == 4;
-        if (!ok)
-            return fail(TG_EINVAL, "fixed IV of %u bytes gives no 12-byte nonce for this suite "
-                        "(TLS 1.3: 12; TLS 1.2 AES: 4; TLS 1.2 ChaCha: 12 or 4)", ivl);
-    }
+    int rc = check_framing(k, r->version, r->fixed_iv_len);
+    if (rc) return rc;
     if (!r->data || !r->data_off || !r->data_len || !r->ctype || !r->wire || !r->wire_off ||
         !r->wire_len || (!seal && !r->status))
         return fail(TG_EINVAL, "null device array");
-    int rc = select_device(k);
-    if (rc) return rc;
+    if ((rc = select_device(k))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     ScratchAlloc alloc;
     tg::RecScratch s;
@@ -447,23 +471,64 @@ int records(tg_key* k, const tg_records* r, void* stream, bool seal) {
     if ((rc = tg_launch_records_prep(*r, seal, aes, k->taglen, s, st)))
         return fail(rc, "framing launch failed");
     tg_batch b;
-    memset(&b, 0, sizeof(b));
-    b.n = r->n;
-    b.len = s.len;
-    b.nonce = s.nonce;
-    b.aad = s.aad;
-    b.aad_stride = 16;
-    b.aad_len = s.aad_len;
-    b.out_off = s.out_abs;          // absolute addresses: out base NULL
-    if (seal) {
-        b.in = r->data;
-        b.in_off = r->data_off;
-    } else {
-        b.in_off = s.in_abs;
-        b.status = s.aead_st;
-    }
+    framing_batch(b, r->n, s, seal, r->data, r->data_off);
     if ((rc = launch(k, b, !seal, st))) return fail(rc, "AEAD launch failed");
     if (!seal && (rc = tg_launch_records_finish(*r, s, st))) return fail(rc, "finish launch failed");
+    return TG_OK;
+}
+
+// tg_seal_session_records / tg_open_session_records: the framing of
+// records() with a session per record.  Argument errors come first, before
+// any HIP call.  Counter mode runs the rank pass (sessions.hip) into a
+// per-call array of sequence numbers; explicit mode reads the caller's.
+int session_records(tg_key* k, const tg_session_records* r, void* stream, bool seal) {
+    if (!r) return fail(TG_EINVAL, "null argument");
+    if ((r->seq != nullptr) == (r->seq_next != nullptr))
+        return fail(TG_EINVAL, "exactly one of seq (explicit numbers) and seq_next (per-session "
+                    "counters) must be given, got %s", r->seq ? "both" : "neither");
+    // one limit for both modes, checked before anything is launched: the
+    // rank pass and the key-table plans index records with 32 bits
+    if (r->n > 0xfffffffeull) return fail(TG_EINVAL, "at most 2^32 - 2 records per call");
+    if (!k) return fail(TG_EINVAL, "null argument");
+    if (r->n == 0) return TG_OK;
+    if (!r->iv_table || !r->session || !r->data || !r->data_off || !r->data_len || !r->ctype ||
+        !r->wire || !r->wire_off || !r->wire_len || (!seal && !r->status))
+        return fail(TG_EINVAL, "null device array");
+    if (r->nsessions != k->nkeys)
+        return fail(TG_EINVAL, "nsessions (%llu) must equal the key handle's nkeys (%llu)",
+                    (unsigned long long)r->nsessions, (unsigned long long)k->nkeys);
+    int rc = check_framing(k, r->version, r->fixed_iv_len);
+    if (rc) return rc;
+    if ((rc = select_device(k))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ScratchAlloc alloc, seq_alloc;
+    tg::RecScratch s;
+    if ((rc = records_scratch(r->n, st, alloc, s))) return rc;
+    const uint64_t* seq = r->seq;
+    if (r->seq_next) {
+        size_t rank_bytes = 0;
+        if ((rc = tg_session_rank(nullptr, r->n, r->nsessions, nullptr, nullptr, nullptr, &rank_bytes, st)))
+            return fail(rc, "rank pass sizing failed");
+        const size_t seq_bytes = (r->n * sizeof(uint64_t) + 255) & ~(size_t)255;
+        seq_alloc.s = st;
+        if (tg::stream_alloc(&seq_alloc.base, seq_bytes + rank_bytes, st))
+            return fail(TG_EHIP, "scratch allocation failed");
+        uint64_t* ranked = static_cast<uint64_t*>(seq_alloc.base);
+        if ((rc = tg_session_rank(r->session, r->n, r->nsessions, r->seq_next, ranked,
+                                  static_cast<uint8_t*>(seq_alloc.base) + seq_bytes, &rank_bytes, st)))
+            return fail(rc, "rank pass launch failed");
+        seq = ranked;
+    }
+    const bool aes = k->alg != TG_CHACHA20_POLY1305;
+    if ((rc = tg_launch_session_records_prep(*r, seq, seal, aes, k->taglen, s, st)))
+        return fail(rc, "framing launch failed");
+    tg_batch b;
+    framing_batch(b, r->n, s, seal, r->data, r->data_off);
+    // launch() takes no key index for a single key; the prep kernel has
+    // already emptied the records whose session is out of range
+    if (k->nkeys > 1) b.key_idx = r->session;
+    if ((rc = launch(k, b, !seal, st))) return fail(rc, "AEAD launch failed");
+    if (!seal && (rc = tg_launch_session_records_finish(*r, s, st))) return fail(rc, "finish launch failed");
     return TG_OK;
 }
 
@@ -1016,6 +1081,14 @@ int tg_seal_records(tg_key* k, const tg_records* r, void* stream) {
 
 int tg_open_records(tg_key* k, const tg_records* r, void* stream) {
     return records(k, r, stream, false);
+}
+
+int tg_seal_session_records(tg_key* k, const tg_session_records* r, void* stream) {
+    return session_records(k, r, stream, true);
+}
+
+int tg_open_session_records(tg_key* k, const tg_session_records* r, void* stream) {
+    return session_records(k, r, stream, false);
 }
 
 int tg_make_nonces(int mode, const uint8_t* iv, size_t ivlen, uint64_t seq0, uint64_t n,

@@ -308,6 +308,8 @@ struct RecScratch {
     uint8_t* st;          // framing status from prep (open)
     uint8_t* aead_st;     // AEAD open status
     uint8_t* dummy;       // 32 zero bytes: AEAD input of publicly-invalid records
+    uint8_t* sink;        // 32 bytes nobody reads: AEAD output of skipped records
+                          // (tg_session_records, session out of range)
 };
 
 // The per-slot keystream precompute of the AES-GCM octet / pair jobs
@@ -432,6 +434,18 @@ int tg_launch_chacha(const tg::ChachaKeyDev* keys, uint64_t nkeys, const tg_batc
 int tg_launch_records_prep(const tg_records& r, bool seal, bool aes, int taglen,
                            const tg::RecScratch& s, hipStream_t st);
 int tg_launch_records_finish(const tg_records& r, const tg::RecScratch& s, hipStream_t st);
+// The many-session framing kernels (records.hip); seq: per-record sequence
+// numbers (the caller's, or tg_session_rank's).
+int tg_launch_session_records_prep(const tg_session_records& r, const uint64_t* seq, bool seal, bool aes,
+                                   int taglen, const tg::RecScratch& s, hipStream_t st);
+int tg_launch_session_records_finish(const tg_session_records& r, const tg::RecScratch& s, hipStream_t st);
+// Counter-mode sequence numbers of a many-session batch (sessions.hip):
+// seq[i] = seq_next[session[i]] + the count of earlier records of the same
+// session, for every record with session[i] < nsessions (the others: seq[i]
+// not written, nothing consumed); then seq_next[s] += session s's record
+// count.  n < 2^32.  scratch NULL: *bytes receives the scratch size.
+int tg_session_rank(const uint32_t* session, uint64_t n, uint64_t nsessions, uint64_t* seq_next,
+                    uint64_t* seq, void* scratch, size_t* bytes, hipStream_t s);
 int tg_launch_hkdf(int hashlen, const tg::HkdfMsg& msg, const uint8_t* secrets, uint64_t n,
                    uint8_t* out, hipStream_t s);
 int tg_launch_aes_setup(int keylen, int layout, const uint8_t* keys, uint64_t n, void* out,

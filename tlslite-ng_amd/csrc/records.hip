@@ -11,6 +11,9 @@
 // ct || tag straight into the wire record (no payload copy).  Open: prep
 // parses and checks headers, the AEAD kernel writes the plaintext straight
 // into the data buffer, and a finish kernel de-pads and settles the status.
+// The same per-record code serves one connection (tg_records: one fixed IV,
+// sequence numbers seq0 + i) and many sessions in one batch
+// (tg_session_records: IV row and sequence number per record).
 #include "common.h"
 
 namespace tg {
@@ -29,19 +32,54 @@ __device__ __forceinline__ void put_be64(uint8_t* p, uint64_t v) {
     for (int k = 0; k < 8; ++k) p[k] = (uint8_t)(v >> (56 - 8 * k));
 }
 
+// The fixed IV as three little-endian words of its 12 bytes (a 4-byte IV
+// fills word 0 only).
+struct IvWords {
+    uint32_t w[3];
+};
+
+__device__ __forceinline__ uint32_t le32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+__device__ __forceinline__ IvWords iv_words(const tg_records& r) {
+    return IvWords{{le32(r.fixed_iv), le32(r.fixed_iv + 4), le32(r.fixed_iv + 8)}};
+}
+
+// Row ``sess`` of the packed IV table: word loads when the table is 4-byte
+// aligned (rows of 4 or 12 bytes then are too), else bytes.
+__device__ __forceinline__ IvWords iv_words(const tg_session_records& r, uint32_t sess) {
+    const uint8_t* p = r.iv_table + (uint64_t)sess * r.fixed_iv_len;
+    IvWords iv{{0, 0, 0}};
+    if (((uintptr_t)r.iv_table & 3u) == 0) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        iv.w[0] = q[0];
+        if (r.fixed_iv_len == 12) {
+            iv.w[1] = q[1];
+            iv.w[2] = q[2];
+        }
+    } else {
+        iv.w[0] = le32(p);
+        if (r.fixed_iv_len == 12) {
+            iv.w[1] = le32(p + 4);
+            iv.w[2] = le32(p + 8);
+        }
+    }
+    return iv;
+}
+
 // RecordLayer._getNonce: XOR form for TLS 1.3 and for ChaCha with a 12-byte
 // fixed IV (RFC 7905); concatenation form otherwise (TLS 1.2 AES-GCM).
-__device__ __forceinline__ void rec_nonce(const tg_records& r, bool xor_form, uint64_t seq,
-                                          uint8_t* out) {
+__device__ __forceinline__ void rec_nonce(const IvWords& iv, bool xor_form, uint64_t seq, uint8_t* out) {
     if (xor_form) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
             const uint8_t s = k < 4 ? 0 : (uint8_t)(seq >> (8 * (11 - k)));
-            out[k] = r.fixed_iv[k] ^ s;
+            out[k] = (uint8_t)(iv.w[k >> 2] >> (8 * (k & 3))) ^ s;
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = r.fixed_iv[k];
+        for (int k = 0; k < 4; ++k) out[k] = (uint8_t)(iv.w[0] >> (8 * k));
         put_be64(out + 4, seq);
     }
 }
@@ -49,29 +87,29 @@ __device__ __forceinline__ void rec_nonce(const tg_records& r, bool xor_form, ui
 // rec_nonce as three little-endian words of its 12 bytes, for one aligned
 // row store instead of twelve byte stores (the prep kernels' rows are
 // 4-byte aligned: RecScratch).
-__device__ __forceinline__ uint32_t iv_word(const tg_records& r, int q) {
-    return (uint32_t)r.fixed_iv[4 * q] | ((uint32_t)r.fixed_iv[4 * q + 1] << 8) |
-           ((uint32_t)r.fixed_iv[4 * q + 2] << 16) | ((uint32_t)r.fixed_iv[4 * q + 3] << 24);
-}
-__device__ __forceinline__ void rec_nonce_row(const tg_records& r, bool xor_form, uint64_t seq, uint32_t* out) {
+__device__ __forceinline__ void rec_nonce_row(const IvWords& iv, bool xor_form, uint64_t seq, uint32_t* out) {
     // be64(seq) as the LE words of bytes 4..11
     const uint32_t hi = bswap32((uint32_t)(seq >> 32)), lo = bswap32((uint32_t)seq);
     if (xor_form) {
-        out[0] = iv_word(r, 0);
-        out[1] = iv_word(r, 1) ^ hi;
-        out[2] = iv_word(r, 2) ^ lo;
+        out[0] = iv.w[0];
+        out[1] = iv.w[1] ^ hi;
+        out[2] = iv.w[2] ^ lo;
     } else {
-        out[0] = iv_word(r, 0);
+        out[0] = iv.w[0];
         out[1] = hi;
         out[2] = lo;
     }
 }
 
-__global__ void seal_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= r.n) return;
+// The per-record framing, shared by the single-connection kernels (fixed IV
+// in the struct, sequence number seq0 + i) and the many-session kernels (IV
+// row and sequence number of the record's session).  R is tg_records or
+// tg_session_records: the data / wire arrays have the same names and meaning
+// in both.
+template <class R>
+__device__ __forceinline__ void seal_one(const R& r, uint64_t i, uint64_t seq, const IvWords& iv, bool aes,
+                                         uint32_t taglen, const RecScratch& s) {
     const bool tls13 = r.version == TG_TLS13;
-    const uint64_t seq = r.seq0 + i;
     const uint32_t L = r.data_len[i];
     const uint8_t ct = r.ctype[i];
     uint8_t* d = r.data + r.data_off[i];
@@ -93,7 +131,7 @@ __global__ void seal_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s)
     r.wire_len[i] = 5 + body;
     s.out_abs[i] = (uint64_t)(uintptr_t)(w + 5 + explicit_len);
     s.len[i] = inner;
-    rec_nonce_row(r, tls13 || (!aes && r.fixed_iv_len == 12), seq, reinterpret_cast<uint32_t*>(s.nonce + 12 * i));
+    rec_nonce_row(iv, tls13 || (!aes && r.fixed_iv_len == 12), seq, reinterpret_cast<uint32_t*>(s.nonce + 12 * i));
     // the AAD row as one 16-byte store (LE words of its bytes, zero-padded)
     uint4 a;
     if (tls13) {  // AAD = the record header, length = inner + tag (:546-552)
@@ -107,11 +145,10 @@ __global__ void seal_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s)
     *reinterpret_cast<uint4*>(s.aad + 16 * i) = a;
 }
 
-__global__ void open_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= r.n) return;
+template <class R>
+__device__ __forceinline__ void open_one(const R& r, uint64_t i, uint64_t seq, const IvWords& iv, bool aes,
+                                         uint32_t taglen, const RecScratch& s) {
     const bool tls13 = r.version == TG_TLS13;
-    const uint64_t seq = r.seq0 + i;
     const uint8_t* w = r.wire + r.wire_off[i];
     const uint32_t wl = r.wire_len[i];
     const uint32_t buf_len = wl >= 5 ? wl - 5 : 0;
@@ -140,10 +177,10 @@ __global__ void open_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s)
     s.out_abs[i] = (uint64_t)(uintptr_t)(r.data + r.data_off[i]);
     uint8_t* n = s.nonce + 12 * i;
     if (explicit_len && st == TG_REC_OK) {   // fixed IV || explicit nonce (:790)
-        for (int k = 0; k < 4; ++k) n[k] = r.fixed_iv[k];
+        for (int k = 0; k < 4; ++k) n[k] = (uint8_t)(iv.w[0] >> (8 * k));
         for (int k = 0; k < 8; ++k) n[4 + k] = w[5 + k];
     } else {
-        rec_nonce(r, tls13 || (!aes && r.fixed_iv_len == 12), seq, n);
+        rec_nonce(iv, tls13 || (!aes && r.fixed_iv_len == 12), seq, n);
     }
     uint8_t* a = s.aad + 16 * i;
     if (tls13) {
@@ -159,9 +196,8 @@ __global__ void open_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s)
     }
 }
 
-__global__ void open_finish(tg_records r, RecScratch s) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= r.n) return;
+template <class R>
+__device__ __forceinline__ void finish_one(const R& r, uint64_t i, const RecScratch& s) {
     const bool tls13 = r.version == TG_TLS13;
     uint8_t st = s.st[i];
     if (st == TG_REC_OK && s.aead_st[i] != 1) st = TG_REC_BAD_MAC;         // :822-823
@@ -190,6 +226,75 @@ __global__ void open_finish(tg_records r, RecScratch s) {
     r.data_len[i] = plen;
     r.ctype[i] = type;
     r.status[i] = st;
+}
+
+__global__ void seal_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    seal_one(r, i, r.seq0 + i, iv_words(r), aes, taglen, s);
+}
+
+__global__ void open_prep(tg_records r, bool aes, uint32_t taglen, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    open_one(r, i, r.seq0 + i, iv_words(r), aes, taglen, s);
+}
+
+__global__ void open_finish(tg_records r, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    finish_one(r, i, s);
+}
+
+// Many sessions (tg_session_records).  ``seq``: the per-record sequence
+// numbers -- the caller's array in explicit mode, the rank pass's output
+// (sessions.hip) in counter mode.  A record whose session is out of range
+// touches neither table: its AEAD job is an empty message from the dummy
+// input into the sink (key tables skip it anyway; a single-key handle has no
+// key index to skip by), so nothing reaches wire or data.
+__device__ __forceinline__ void skip_one(uint64_t i, const RecScratch& s) {
+    s.in_abs[i] = (uint64_t)(uintptr_t)s.dummy;
+    s.out_abs[i] = (uint64_t)(uintptr_t)s.sink;
+    s.len[i] = 0;
+    s.aad_len[i] = 0;
+    uint32_t* n = reinterpret_cast<uint32_t*>(s.nonce + 12 * i);
+    n[0] = n[1] = n[2] = 0;
+}
+
+__global__ void seal_prep_sessions(tg_session_records r, const uint64_t* __restrict__ seq, bool aes,
+                                   uint32_t taglen, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    const uint32_t sess = r.session[i];
+    if (sess >= r.nsessions) {
+        skip_one(i, s);
+        r.wire_len[i] = 0;
+        return;
+    }
+    const uint64_t q = seq[i];
+    if (r.seq_out) r.seq_out[i] = q;
+    seal_one(r, i, q, iv_words(r, sess), aes, taglen, s);
+}
+
+__global__ void open_prep_sessions(tg_session_records r, const uint64_t* __restrict__ seq, bool aes,
+                                   uint32_t taglen, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    const uint32_t sess = r.session[i];
+    if (sess >= r.nsessions) {
+        skip_one(i, s);
+        s.st[i] = TG_REC_BAD_SESSION;   // open_finish_sessions: length and type 0
+        return;
+    }
+    const uint64_t q = seq[i];
+    if (r.seq_out) r.seq_out[i] = q;
+    open_one(r, i, q, iv_words(r, sess), aes, taglen, s);
+}
+
+__global__ void open_finish_sessions(tg_session_records r, RecScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    finish_one(r, i, s);
 }
 
 // tg_gather: one workgroup per range; 16-byte vector copies when source and
@@ -234,6 +339,24 @@ int tg_launch_records_prep(const tg_records& r, bool seal, bool aes, int taglen,
 int tg_launch_records_finish(const tg_records& r, const tg::RecScratch& s, hipStream_t st) {
     const uint64_t blocks = (r.n + tg::kRecThreads - 1) / tg::kRecThreads;
     hipLaunchKernelGGL(tg::open_finish, dim3((unsigned)blocks), dim3(tg::kRecThreads), 0, st, r, s);
+    return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
+}
+
+int tg_launch_session_records_prep(const tg_session_records& r, const uint64_t* seq, bool seal, bool aes,
+                                   int taglen, const tg::RecScratch& s, hipStream_t st) {
+    const uint64_t blocks = (r.n + tg::kRecThreads - 1) / tg::kRecThreads;
+    if (seal)
+        hipLaunchKernelGGL(tg::seal_prep_sessions, dim3((unsigned)blocks), dim3(tg::kRecThreads), 0, st, r, seq,
+                           aes, (uint32_t)taglen, s);
+    else
+        hipLaunchKernelGGL(tg::open_prep_sessions, dim3((unsigned)blocks), dim3(tg::kRecThreads), 0, st, r, seq,
+                           aes, (uint32_t)taglen, s);
+    return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
+}
+
+int tg_launch_session_records_finish(const tg_session_records& r, const tg::RecScratch& s, hipStream_t st) {
+    const uint64_t blocks = (r.n + tg::kRecThreads - 1) / tg::kRecThreads;
+    hipLaunchKernelGGL(tg::open_finish_sessions, dim3((unsigned)blocks), dim3(tg::kRecThreads), 0, st, r, s);
     return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
 }
 

@@ -32,14 +32,15 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_memcpy_d2h", "tg_stream_sync", "tg_seal_records", "tg_open_records",
            "tg_hkdf_expand_label", "tg_key_create_device", "tg_scan_records", "tg_gather",
            "tg_selftest_poly1305", "tg_selftest_ghash", "tg_set_option", "tg_get_option",
-           "tg_scratch_info", "tg_scratch_trim", "tg_helper_info", "tg_host_copy", "tg_host_copy_rows")
+           "tg_scratch_info", "tg_scratch_trim", "tg_helper_info", "tg_host_copy", "tg_host_copy_rows",
+           "tg_seal_session_records", "tg_open_session_records")
 
 TG_TLS12 = 0x0303
 TG_TLS13 = 0x0304
 # per-record status of tg_open_records (include/tlsgpu.h TG_REC_*)
 REC_STATUS = {0: "ok", 1: "bad_record_mac", 2: "truncated", 3: "length_mismatch",
               4: "unexpected_content_type", 5: "illegal_version", 6: "no_content_type",
-              7: "record_overflow"}
+              7: "record_overflow", 8: "bad_session"}
 
 
 class TgBatch(ctypes.Structure):
@@ -74,6 +75,31 @@ class TgRecords(ctypes.Structure):
         ("fixed_iv", ctypes.c_uint8 * 12),
         ("recv_limit", ctypes.c_uint32),
         ("seq0", ctypes.c_uint64),
+        ("data", ctypes.c_void_p),
+        ("data_off", ctypes.c_void_p),
+        ("data_len", ctypes.c_void_p),
+        ("ctype", ctypes.c_void_p),
+        ("pad_len", ctypes.c_void_p),
+        ("wire", ctypes.c_void_p),
+        ("wire_off", ctypes.c_void_p),
+        ("wire_len", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
+class TgSessionRecords(ctypes.Structure):
+    """``struct tg_session_records`` (include/tlsgpu.h)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("version", ctypes.c_uint32),
+        ("fixed_iv_len", ctypes.c_uint32),
+        ("recv_limit", ctypes.c_uint32),
+        ("nsessions", ctypes.c_uint64),
+        ("iv_table", ctypes.c_void_p),
+        ("session", ctypes.c_void_p),
+        ("seq", ctypes.c_void_p),
+        ("seq_next", ctypes.c_void_p),
+        ("seq_out", ctypes.c_void_p),
         ("data", ctypes.c_void_p),
         ("data_off", ctypes.c_void_p),
         ("data_len", ctypes.c_void_p),
@@ -147,6 +173,9 @@ def load():
         l.tg_host_copy.argtypes = [p, p, sz, i]
         l.tg_host_copy_rows.argtypes = [p, sz, p, sz, sz, sz, i]
         l.tg_helper_info.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_seal_session_records"):
+        l.tg_seal_session_records.argtypes = [p, ctypes.POINTER(TgSessionRecords), p]
+        l.tg_open_session_records.argtypes = [p, ctypes.POINTER(TgSessionRecords), p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):
