@@ -10,6 +10,10 @@
 //                          each in an exactly-sized heap buffer so any read
 //                          past the end trips ASan; one result line per case
 //                          for the Python restatement of RecordSocket.recv.
+//   host_check hkdf        HKDF label cases from stdin (see check_hkdf), label
+//                          and context each in an exactly-sized heap buffer;
+//                          one line per case for the Python restatement of
+//                          HkdfLabel and the SHA padding.
 //   host_check canary      a deliberate heap over-read (must abort under ASan).
 //   host_check fuzz N S    N random / truncated / oversize header streams
 //                          (seed S) through the scanner with invariant checks.
@@ -219,6 +223,34 @@ static int fuzz(long iters, uint64_t seed) {
     return g_fail;
 }
 
+// One packer case on stdin: u32 hashlen, u32 outlen, u32 labellen, u32 ctxlen
+// (little-endian), then the label and the context.  Output: "ok <nblocks>
+// <outlen> <word> ..." (the nblocks blocks' words, hex) or "refused".
+static int check_hkdf() {
+    uint32_t hdr[4];
+    while (fread(hdr, 4, 4, stdin) == 4) {
+        uint8_t* label = hdr[2] ? (uint8_t*)malloc(hdr[2]) : nullptr;
+        uint8_t* ctx = hdr[3] ? (uint8_t*)malloc(hdr[3]) : nullptr;
+        CHECK((!hdr[2] || fread(label, 1, hdr[2], stdin) == hdr[2]) &&
+              (!hdr[3] || fread(ctx, 1, hdr[3], stdin) == hdr[3]), "short case");
+        HkdfMsg* msg = (HkdfMsg*)malloc(sizeof(HkdfMsg));
+        memset(msg, 0xa5, sizeof(*msg));
+        if (host::hkdf_message((int)hdr[0], label, hdr[2], ctx, hdr[3], hdr[1], msg) == 0) {
+            const uint32_t words = msg->nblocks * (hdr[0] == 32 ? 16u : 32u);
+            CHECK(words <= 64, "nblocks %u", msg->nblocks);
+            printf("ok %u %u", msg->nblocks, msg->outlen);
+            for (uint32_t w = 0; w < words && w < 64; ++w) printf(" %08x", msg->words[w]);
+            printf("\n");
+        } else {
+            printf("refused\n");
+        }
+        free(msg);
+        free(label);
+        free(ctx);
+    }
+    return g_fail;
+}
+
 // tg::host::parallel_copy(_rows) (hostcopy.cpp) into exactly-sized heap
 // buffers: every split (one row by bytes, rows contiguous and strided, 1 to
 // 12 threads, sizes around the 1 MiB chunk and 4 KiB boundaries) against a
@@ -264,6 +296,7 @@ int main(int argc, char** argv) {
         return f ? 1 : 0;
     }
     if (argc >= 2 && !strcmp(argv[1], "scan")) return check_scan() ? 1 : 0;
+    if (argc >= 2 && !strcmp(argv[1], "hkdf")) return check_hkdf() ? 1 : 0;
     if (argc >= 2 && !strcmp(argv[1], "canary")) {   // the sanitizer is live: a 1-byte over-read
         uint8_t* p = (uint8_t*)malloc(5);
         memset(p, 23, 5);
@@ -272,6 +305,6 @@ int main(int argc, char** argv) {
         return v == 0 ? 3 : 4;
     }
     if (argc >= 4 && !strcmp(argv[1], "fuzz")) return fuzz(atol(argv[2]), strtoull(argv[3], 0, 10)) ? 1 : 0;
-    fprintf(stderr, "usage: host_check keys | scan < cases | fuzz N SEED\n");
+    fprintf(stderr, "usage: host_check keys | scan < cases | hkdf < cases | fuzz N SEED\n");
     return 2;
 }

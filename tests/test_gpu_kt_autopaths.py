@@ -1,5 +1,5 @@
 """GPU: the key-table AES-GCM paths ``auto`` picks for one-length batches
-(api.hip launch_gcm_table), every record against the C oracle
+(dispatch.hip launch_gcm_table), every record against the C oracle
 (tests/fullcheck.py), then opened back with tampered records
 (aesgcm.py:101-154 per record, keys by key_idx as RecordLayer holds one
 cipher per connection state):

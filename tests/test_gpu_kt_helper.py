@@ -6,7 +6,7 @@ key-grouped kernel.  The key-table hybrid (the default) takes the short
 records (< 2 048 B) itself once its long jobs are taken; with the bitsliced
 key-grouped kernel (option kt_hybrid -1) and the other long kernels, the
 short ones go to the lane kernel on a helper stream forked from the caller's
-stream (aes_gcm_bs8.hip launch_kt, api.hip helper_fork / helper_join).
+stream (aes_gcm_bs8.hip launch_kt, runtime.hip helper_fork / helper_join).
 Round 5 had ONE helper per device: a second caller's short records queued
 behind the first caller's, so the second caller's stream waited for the
 first one's.  Here:

@@ -2,7 +2,7 @@
 (copy.copy shares the device key, as recordlayer.py:262 / :913 copy the
 cipher state) used from several threads at once.  ctypes releases the GIL
 around every tg_seal / tg_open, so the calls really overlap; each takes its
-own staging slot (api.hip take_stage), so every output must still equal the
+own staging slot (keys.hip take_stage), so every output must still equal the
 oracle's."""
 import copy
 import threading

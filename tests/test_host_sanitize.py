@@ -1,10 +1,13 @@
 """libtlsgpu's host half (csrc/host.cpp: AES key schedules, GHASH tables, the
-GcmKeyDev image, the record scanner) built with g++ -fsanitize=address,undefined
+GcmKeyDev image, the record scanner, the HKDF label packer) built with g++ -fsanitize=address,undefined
 and driven by tests/native/host_check.cpp (no GPU).  The scanner runs in
 exactly-sized heap buffers against the RecordSocket.recv restatement of
 test_ingest_host.py (recordlayer.py:169-237) on random, truncated and
 oversize-header streams; the C++ fuzz mode adds 10^5 cases per seed with
-invariant checks."""
+invariant checks.  The packer's message blocks are checked against HkdfLabel and
+the SHA padding, and through HMAC against oracle/keysetup.py's
+HKDF-Expand-Label (cryptomath.py:155-173)."""
+import hmac
 import os
 import random
 import shutil
@@ -13,6 +16,7 @@ import subprocess
 
 import pytest
 
+from oracle import keysetup as K
 from test_ingest_host import _stream, _walk
 from tlsgpu import ingest
 
@@ -137,3 +141,65 @@ def test_scanner_matches_restatement(host_check):
         want = _expect(buf, mb, mn)
         got = line if line.startswith("ok") else " ".join(line.split()[:3])
         assert got == want, (mb, mn, len(buf))
+
+
+HKDF_SECRET = bytes(range(1, 49))
+HKDF_LABELS = [(b"key", b""), (b"iv", b""), (b"traffic upd", b""),
+               (b"c hs traffic", bytes(range(100, 132))), (b"c hs traffic", bytes(range(100, 148)))]
+
+
+def _hkdf_cases():
+    """(hashlen, outlen, label, context, accepted): the labels of the key
+    schedule at every output length, then the acceptance boundary
+    9 + labellen + 2 + ctxlen <= 200 and the one-byte length fields."""
+    out = []
+    for hashlen in (32, 48):
+        for label, ctx in HKDF_LABELS:
+            for outlen in sorted({12, 16, 32, hashlen}):
+                out.append((hashlen, outlen, label, ctx, True))
+        ctx = bytes(range(32))
+        out.append((hashlen, hashlen, b"L" * 157, ctx, True))
+        out.append((hashlen, hashlen, b"L" * 158, ctx, False))
+        out.append((hashlen, hashlen, b"L" * 250, b"", False))
+        out.append((hashlen, hashlen, b"key", bytes(256), False))
+    return out
+
+
+@pytest.fixture(scope="module")
+def hkdf_lines(host_check):
+    cases = _hkdf_cases()
+    data = b"".join(struct.pack("<IIII", h, o, len(lb), len(cx)) + lb + cx for h, o, lb, cx, _ in cases)
+    r = _run(host_check, "hkdf", stdin=data)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = r.stdout.decode().splitlines()
+    assert len(lines) == len(cases)
+    return list(zip(cases, lines))
+
+
+def test_hkdf_packer_acceptance(hkdf_lines):
+    for (hashlen, outlen, label, ctx, accepted), line in hkdf_lines:
+        assert line.startswith("ok ") == accepted, (hashlen, len(label), len(ctx), line[:20])
+        assert accepted or line == "refused"
+
+
+def test_hkdf_packer_matches_reference(hkdf_lines):
+    """The blocks are HkdfLabel || 0x01 with SHA padding whose bit length
+    counts the (K ^ ipad) block in front, and HMAC over the label bytes is
+    the oracle's HKDF-Expand-Label."""
+    for (hashlen, outlen, label, ctx, accepted), line in hkdf_lines:
+        if not accepted:
+            continue
+        f = line.split()
+        nblocks, got_outlen = int(f[1]), int(f[2])
+        msg = b"".join(struct.pack(">I", int(w, 16)) for w in f[3:])
+        block, lenfield, alg = (64, 8, "sha256") if hashlen == 32 else (128, 16, "sha384")
+        info = K.hkdf_label(label, ctx, outlen) + b"\x01"
+        total = -(-(len(info) + 1 + lenfield) // block) * block
+        want = info + b"\x80" + bytes(total - len(info) - 1 - lenfield) + \
+            ((block + len(info)) * 8).to_bytes(lenfield, "big")
+        assert (nblocks, got_outlen, len(msg)) == (total // block, outlen, total)
+        assert msg == want, (hashlen, outlen, label)
+        # the label bytes as the padding's own length field delimits them
+        n = int.from_bytes(msg[-lenfield:], "big") // 8 - block
+        assert hmac.new(HKDF_SECRET[:hashlen], msg[:n], alg).digest()[:outlen] == \
+            K.hkdf_expand_label(HKDF_SECRET[:hashlen], label, ctx, outlen, alg)

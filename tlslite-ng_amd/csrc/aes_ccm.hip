@@ -30,6 +30,7 @@
 #include "aes_bs8.h"
 #include "aes_round.h"
 #include "options.h"
+#include "runtime.h"
 
 namespace tg {
 namespace {
@@ -649,17 +650,19 @@ int launch_hy(const AesKeyDev* key, const tg_batch& b, hipStream_t s) {
     const uint32_t nt = o < 0 ? 0u : o == 0 ? (uint32_t)kCcmHyTDefault : (uint32_t)o;
     if (lds_attr((const void*)ccm_hy_kernel<NR, OPEN, TAG>, (int)kCcmHyLds)) return TG_EHIP;
     if ((b.n + 63) / 64 > 0xffffffffull) return TG_EINVAL;
-    uint32_t* scratch = nullptr;
-    if (stream_alloc((void**)&scratch, kCcmHyScratch, s)) return TG_EHIP;
-    hipLaunchKernelGGL(ccm_hy_setup_kernel, dim3(1), dim3(256), 0, s, key, NR, b, scratch);
+    Scratch scratch(s);
+    if (scratch.alloc(kCcmHyScratch)) return TG_EHIP;
+    uint32_t* queue = scratch.take<uint32_t>(64, 64);                       // word 0
+    const tg_batch* bcopy = scratch.take<tg_batch>(512 - 64, 64);          // word 16
+    const uint4* rows = scratch.take<uint4>(15 * 32 * 4, 256);             // word 128
+    hipLaunchKernelGGL(ccm_hy_setup_kernel, dim3(1), dim3(256), 0, s, key, NR, b, queue);
     int rc = hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
     if (!rc) {
         hipLaunchKernelGGL((ccm_hy_kernel<NR, OPEN, TAG>), dim3((unsigned)device_cus()), dim3(kCcmHyThreads),
-                           kCcmHyLds, s, key, reinterpret_cast<const tg_batch*>(scratch + 16),
-                           reinterpret_cast<const uint4*>(scratch + 128), scratch, nt);
+                           kCcmHyLds, s, key, bcopy, rows, queue, nt);
         rc = hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
     }
-    if (stream_free(scratch, s) && !rc) rc = TG_EHIP;
+    if (scratch.release() && !rc) rc = TG_EHIP;
     return rc;
 }
 
@@ -719,15 +722,9 @@ int launch(const AesKeyDev* keys, uint64_t nkeys, const tg_batch& b, hipStream_t
     }
 }
 
-template <int NR, int TAG, bool TABLE>
-int launch_op(const AesKeyDev* keys, uint64_t nkeys, const tg_batch& b, bool open, hipStream_t s) {
-    return open ? launch<NR, true, TAG, TABLE>(keys, nkeys, b, s) : launch<NR, false, TAG, TABLE>(keys, nkeys, b, s);
-}
-
-template <int NR, bool TABLE>
-int launch_tag(const AesKeyDev* keys, uint64_t nkeys, int taglen, const tg_batch& b, bool open, hipStream_t s) {
-    return taglen == 16 ? launch_op<NR, 16, TABLE>(keys, nkeys, b, open, s)
-                        : launch_op<NR, 8, TABLE>(keys, nkeys, b, open, s);
+template <int NR, bool OPEN, bool TABLE>
+int launch_tag(const AesKeyDev* keys, uint64_t nkeys, int taglen, const tg_batch& b, hipStream_t s) {
+    return taglen == 16 ? launch<NR, OPEN, 16, TABLE>(keys, nkeys, b, s) : launch<NR, OPEN, 8, TABLE>(keys, nkeys, b, s);
 }
 
 }  // namespace
@@ -736,12 +733,8 @@ int launch_tag(const AesKeyDev* keys, uint64_t nkeys, int taglen, const tg_batch
 int tg_launch_ccm(const tg::AesKeyDev* keys, uint64_t nkeys, int rounds, int taglen,
                   const tg_batch& b, bool open, hipStream_t s) {
     if (taglen != 16 && taglen != 8) return TG_EINVAL;
-    const bool table = nkeys > 1;
-    if (rounds == 10)
-        return table ? tg::launch_tag<10, true>(keys, nkeys, taglen, b, open, s)
-                     : tg::launch_tag<10, false>(keys, nkeys, taglen, b, open, s);
-    if (rounds == 14)
-        return table ? tg::launch_tag<14, true>(keys, nkeys, taglen, b, open, s)
-                     : tg::launch_tag<14, false>(keys, nkeys, taglen, b, open, s);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) {
+        return nkeys > 1 ? tg::launch_tag<nr(), op(), true>(keys, nkeys, taglen, b, s)
+                         : tg::launch_tag<nr(), op(), false>(keys, nkeys, taglen, b, s);
+    });
 }

@@ -26,6 +26,7 @@
 #include "ghash.h"
 #include "gcm_lane.h"
 #include "options.h"
+#include "runtime.h"
 
 namespace tg {
 namespace {
@@ -597,39 +598,21 @@ int tg_launch_table_hpow(const tg::GcmTableKey* keys, uint64_t n, uint4* hpow, h
 
 int tg_launch_gcm_table_lane(const tg::GcmTableKey* keys, uint64_t nkeys, int rounds, const tg_batch& b,
                              bool open, hipStream_t s, const uint32_t* order, const uint32_t* first) {
-    if (rounds == 10)
-        return open ? tg::launch_table_v<10, true>(keys, nkeys, b, s, order, first)
-                    : tg::launch_table_v<10, false>(keys, nkeys, b, s, order, first);
-    if (rounds == 14)
-        return open ? tg::launch_table_v<14, true>(keys, nkeys, b, s, order, first)
-                    : tg::launch_table_v<14, false>(keys, nkeys, b, s, order, first);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) {
+        return tg::launch_table_v<nr(), op()>(keys, nkeys, b, s, order, first);
+    });
 }
 
 int tg_launch_gcm_table_wave(const tg::GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, int rounds,
                              const tg_batch& b, bool open, hipStream_t s, bool t4, const uint32_t* order,
                              const uint32_t* count) {
-#define TG_TW(NR, OP, T)                                                                           \
-    return tg::launch_table_wave<NR, OP, T>(keys, nkeys, hpow, b, s, order, count)
-    if (rounds == 10) {
-        if (open) { if (t4) TG_TW(10, true, true); TG_TW(10, true, false); }
-        if (t4) TG_TW(10, false, true);
-        TG_TW(10, false, false);
-    }
-    if (rounds == 14) {
-        if (open) { if (t4) TG_TW(14, true, true); TG_TW(14, true, false); }
-        if (t4) TG_TW(14, false, true);
-        TG_TW(14, false, false);
-    }
-#undef TG_TW
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) {
+        return t4 ? tg::launch_table_wave<nr(), op(), true>(keys, nkeys, hpow, b, s, order, count)
+                  : tg::launch_table_wave<nr(), op(), false>(keys, nkeys, hpow, b, s, order, count);
+    });
 }
 
 int tg_launch_gcm(const tg::GcmKeyDev* key, int rounds, const tg_batch& b, bool open,
                   hipStream_t s, const uint32_t* order) {
-    if (rounds == 10)
-        return open ? tg::launch<10, true>(key, b, s, order) : tg::launch<10, false>(key, b, s, order);
-    if (rounds == 14)
-        return open ? tg::launch<14, true>(key, b, s, order) : tg::launch<14, false>(key, b, s, order);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) { return tg::launch<nr(), op()>(key, b, s, order); });
 }

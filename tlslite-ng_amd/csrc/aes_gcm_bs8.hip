@@ -36,6 +36,7 @@
 #include "gcm_lane.h"
 #include "ghash.h"
 #include "options.h"
+#include "runtime.h"
 
 namespace tg {
 namespace {
@@ -869,7 +870,7 @@ int launch_hy(const GcmKeyDev* key, const tg_batch& b, hipStream_t s, const uint
     if (lds_attr(fn, (int)kHyLds)) return TG_EHIP;
     // The launch's scratch -- job counter and batch copy (256 bytes), then two
     // 16-byte keystream blocks per record (hy_mask_kernel) -- comes from the
-    // per-launch scratch cache (api.hip stream_alloc: a buffer is reused once
+    // per-launch scratch cache (runtime.h Scratch: a buffer is reused once
     // the launches behind it have completed, or at once on the same stream)
     // and goes back behind the kernel: launches on different streams
     // (hipStreamPerThread included) never share it, and memory is bounded by
@@ -880,15 +881,15 @@ int launch_hy(const GcmKeyDev* key, const tg_batch& b, hipStream_t s, const uint
 #else
     const uint64_t mrec = b.n;
 #endif
-    uint8_t* scratch = nullptr;
-    if (stream_alloc((void**)&scratch, 256 + 32 * mrec, s)) return TG_EHIP;
-    uint4* masks = mrec ? reinterpret_cast<uint4*>(scratch + 256) : nullptr;
-    uint32_t* queue = reinterpret_cast<uint32_t*>(scratch);
-    tg_batch* bcopy = reinterpret_cast<tg_batch*>(scratch + 64);
+    Scratch scratch(s);
+    if (scratch.alloc(256 + 32 * mrec)) return TG_EHIP;
+    uint32_t* queue = scratch.take<uint32_t>(64, 64);
+    tg_batch* bcopy = scratch.take<tg_batch>(256 - 64, 64);
+    uint4* masks = mrec ? scratch.take<uint4>(32 * mrec, 256) : nullptr;
     hipLaunchKernelGGL(hy_setup_kernel, dim3(1), dim3(64), 0, s, b, queue, bcopy);
     int rc = hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
     if (!rc) rc = launch_hy_kernels<NR, OPEN>(key, b, s, order, nt, prio, small, queue, bcopy, masks);
-    if (stream_free(scratch, s) && !rc) rc = TG_EHIP;
+    if (scratch.release() && !rc) rc = TG_EHIP;
     return rc;
 }
 
@@ -1236,7 +1237,7 @@ int launch_kt_jobs(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, c
 // itself over those records once its long jobs are taken: a separate lane
 // kernel ran 250-610 us alone after it (round 6, profiles/r06/z3/).  Beside
 // the other long kernels the lane kernel runs on a helper stream of the
-// caller's stream (api.hip helper_fork / helper_join: idle or last used by
+// caller's stream (runtime.h helper_fork / helper_join: idle or last used by
 // this caller, so two callers never chain through one helper).  Option
 // kt_overlap -1: one stream.
 template <int NR, bool OPEN>
@@ -1251,19 +1252,20 @@ int launch_kt(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, const 
     int rc = tg_key_job_plan(b.key_idx, b.len, b.fixed_len, b.n, nkeys, split, jobsz, nullptr, nullptr,
                              nullptr, nullptr, nullptr, &plan, s);
     if (rc) return rc;
-    const size_t so = (b.n * 4 + 255) & ~(size_t)255, sj = ((b.n + 1) * 4 + 255) & ~(size_t)255;
+    const size_t so = b.n * 4, sj = (b.n + 1) * 4;
     // the key-table hybrid's per-slot tag masks (kt_mask_kernel) after the plan
-    const size_t sm = hybrid && lpr == 32 ? b.n * 32 + (b.n + 1) * 4 : 0;   // + the jobs' keys
-    const size_t po = (so + sj + 256 + plan + 255) & ~(size_t)255;
-    uint8_t* buf = nullptr;
-    if (stream_alloc((void**)&buf, po + sm, s)) return TG_EHIP;
-    uint32_t* order = reinterpret_cast<uint32_t*>(buf);
-    uint32_t* jobpos = reinterpret_cast<uint32_t*>(buf + so);
-    uint32_t* njobs = reinterpret_cast<uint32_t*>(buf + so + sj);
+    const size_t sm = hybrid && lpr == 32 ? b.n * 32 + sj : 0;   // + the jobs' keys
+    Scratch scratch(s);
+    if (scratch.alloc(align_up(align_up(so, 256) + align_up(sj, 256) + 256 + plan, 256) + sm)) return TG_EHIP;
+    uint32_t* order = scratch.take<uint32_t>(so, 256);
+    uint32_t* jobpos = scratch.take<uint32_t>(sj, 256);
+    uint32_t* njobs = scratch.take<uint32_t>(256, 256);   // word 1: nlong; words 16, 17: the hybrid's queue
     uint32_t* nlong = njobs + 1;
-    uint32_t* jobkey = sm ? reinterpret_cast<uint32_t*>(buf + po + b.n * 32) : nullptr;
+    void* plan_scratch = scratch.take<uint8_t>(plan, 256);
+    uint4* masks = sm ? scratch.take<uint4>(b.n * 32, 256) : nullptr;
+    uint32_t* jobkey = sm ? scratch.take<uint32_t>(sj, 4) : nullptr;
     rc = tg_key_job_plan(b.key_idx, b.len, b.fixed_len, b.n, nkeys, split, jobsz, order, jobpos, njobs, nlong,
-                         buf + so + sj + 256, &plan, s, jobkey);
+                         plan_scratch, &plan, s, jobkey);
     // The short records (plan slots [nlong, n)): the key-table hybrid takes
     // them itself once its long jobs are taken (gcm_kth_kernel).  With the
     // other long kernels they go to the lane kernel, on a helper stream forked
@@ -1285,8 +1287,7 @@ int launch_kt(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, const 
             case 16: rc = launch_kt_jobs<NR, OPEN, 16>(keys, nkeys, hpow, planes, b, s, order, jobpos, njobs, nlong); break;
             case 32:
                 rc = hybrid ? launch_kth<NR, OPEN>(keys, hpow, planes, rot, b, s, order, jobpos, njobs, nlong,
-                                                   njobs + 16, reinterpret_cast<uint4*>(buf + po), jobkey, nkeys,
-                                                   kth_lanes)
+                                                   njobs + 16, masks, jobkey, nkeys, kth_lanes)
                             : launch_kt_jobs<NR, OPEN, 32>(keys, nkeys, hpow, planes, b, s, order, jobpos, njobs,
                                                            nlong);
                 break;
@@ -1296,7 +1297,7 @@ int launch_kt(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, const 
     if (!rc && !kth_lanes) rc = tg_launch_gcm_table_lane(keys, nkeys, NR, b, OPEN, s2 ? s2 : s, order, nlong);
     // rejoin (also after a failed launch: the scratch must outlive both streams' work)
     if (s2 && helper_join(s2, s) && !rc) rc = TG_EHIP;
-    if (stream_free(buf, s)) return TG_EHIP;
+    if (scratch.release() && !rc) rc = TG_EHIP;
     return rc;
 }
 
@@ -1305,32 +1306,20 @@ int launch_kt(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, const 
 
 int tg_launch_gcm_hy(const tg::GcmKeyDev* key, int rounds, const tg_batch& b, bool open,
                      hipStream_t s, const uint32_t* order) {
-    if (rounds == 10)
-        return open ? tg::launch_hy<10, true>(key, b, s, order) : tg::launch_hy<10, false>(key, b, s, order);
-    if (rounds == 14)
-        return open ? tg::launch_hy<14, true>(key, b, s, order) : tg::launch_hy<14, false>(key, b, s, order);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) { return tg::launch_hy<nr(), op()>(key, b, s, order); });
 }
 
 int tg_launch_gcm_bs8(const tg::GcmKeyDev* key, int rounds, const tg_batch& b, bool open,
                       hipStream_t s, const uint32_t* order) {
-    if (rounds == 10)
-        return open ? tg::launch_bs8<10, true>(key, b, s, order) : tg::launch_bs8<10, false>(key, b, s, order);
-    if (rounds == 14)
-        return open ? tg::launch_bs8<14, true>(key, b, s, order) : tg::launch_bs8<14, false>(key, b, s, order);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) { return tg::launch_bs8<nr(), op()>(key, b, s, order); });
 }
 
 int tg_launch_gcm_kt(const tg::GcmTableKey* keys, uint64_t nkeys, const uint4* hpow, const uint32_t* planes,
                      const uint4* rot, int rounds, const tg_batch& b, bool open, hipStream_t s, uint32_t split,
                      int lpr, bool hybrid) {
-    if (rounds == 10)
-        return open ? tg::launch_kt<10, true>(keys, nkeys, hpow, planes, rot, b, s, split, lpr, hybrid)
-                    : tg::launch_kt<10, false>(keys, nkeys, hpow, planes, rot, b, s, split, lpr, hybrid);
-    if (rounds == 14)
-        return open ? tg::launch_kt<14, true>(keys, nkeys, hpow, planes, rot, b, s, split, lpr, hybrid)
-                    : tg::launch_kt<14, false>(keys, nkeys, hpow, planes, rot, b, s, split, lpr, hybrid);
-    return TG_EINVAL;
+    return tg::with_rounds(rounds, open, [&](auto nr, auto op) {
+        return tg::launch_kt<nr(), op()>(keys, nkeys, hpow, planes, rot, b, s, split, lpr, hybrid);
+    });
 }
 
 int tg_launch_kt_planes(const tg::GcmTableKey* keys, uint64_t n, int rounds, uint32_t* planes,

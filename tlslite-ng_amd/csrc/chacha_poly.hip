@@ -17,6 +17,7 @@
 #include "common.h"
 #include "options.h"
 #include "poly1305.h"
+#include "runtime.h"
 
 namespace tg {
 namespace {
@@ -832,13 +833,14 @@ bool wave_path(uint64_t n) {
 }
 
 // The octet kernel (single key): the one-time keys and powers of r into
-// per-launch scratch (api.hip stream_alloc), then the records.
+// per-launch scratch (runtime.h Scratch), then the records.
 template <bool OPEN>
 int launch_octet(const ChachaKeyDev* key, const tg_batch& b, hipStream_t s, const uint32_t* order) {
     const uint64_t groups = (b.n + (kOctetThreads / 8) - 1) / (kOctetThreads / 8);
     if (groups > 0x7fffffffull) return TG_EINVAL;
-    OctetPoly* pw = nullptr;
-    if (stream_alloc((void**)&pw, sizeof(OctetPoly) * b.n, s)) return TG_EHIP;
+    Scratch scratch(s);
+    if (scratch.alloc(sizeof(OctetPoly) * b.n)) return TG_EHIP;
+    OctetPoly* pw = scratch.take<OctetPoly>(sizeof(OctetPoly) * b.n, alignof(OctetPoly));
     hipLaunchKernelGGL(chacha_otk_kernel, dim3((unsigned)((b.n + 255) / 256)), dim3(256), 0, s, key, b, order, pw);
     int rc = hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
     if (!rc) {
@@ -846,7 +848,7 @@ int launch_octet(const ChachaKeyDev* key, const tg_batch& b, hipStream_t s, cons
                            order, pw);
         rc = hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
     }
-    if (stream_free(pw, s) && !rc) rc = TG_EHIP;
+    if (scratch.release() && !rc) rc = TG_EHIP;
     return rc;
 }
 

@@ -9,8 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
+#include <type_traits>
 
+#include "host.h"   // HkdfMsg
 #include "keymath.h"
 #include "tlsgpu.h"
 
@@ -288,15 +289,6 @@ __device__ __forceinline__ uint4 mask_tail(uint4 v, uint32_t n) {
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// The session-independent part of an HKDF-Expand-Label call (keysetup.hip):
-// info || 0x01 and its SHA padding, as big-endian 32-bit words of the message
-// blocks that follow the (K ^ ipad) block.
-struct HkdfMsg {
-    uint32_t nblocks;     // SHA-256: 64-byte blocks (16 words); SHA-384: 128-byte (32 words)
-    uint32_t outlen;      // bytes kept of T(1), <= hash length
-    uint32_t words[64];
-};
-
 // Per-call device scratch of the record-framing entry points (records.hip).
 struct RecScratch {
     uint64_t* in_abs;     // AEAD input address per record (open)
@@ -324,49 +316,16 @@ __host__ __device__ constexpr bool lone_last_block(uint32_t nc) {
     return nc % (8u * LPR) == 1u;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for ``fn`` on the current
-// device, once per (function, device); thread-safe (api.hip).  0 or TG_EHIP.
-int lds_attr(const void* fn, int bytes);
-
-// Per-launch device scratch for launches on stream ``s``: stream_alloc takes
-// a buffer of at least ``bytes`` from a process-wide cache (reused once the
-// launches that last used it have completed, or at once by the next launch
-// on the same stream), stream_free hands it back behind the work queued on
-// ``s`` (api.hip).  0, TG_EHIP, or TG_EINVAL for a pointer not from
-// stream_alloc.
-int stream_alloc(void** p, size_t bytes, hipStream_t s);
-int stream_free(void* p, hipStream_t s);
-void scratch_totals(uint64_t* bytes, uint64_t* buffers);   // tg_scratch_info
-void scratch_trim(size_t keep);                             // tg_scratch_trim
-
-// A helper stream beside caller stream ``s`` (api.hip pool): helper_fork
-// takes one (idle, or last used by ``s``) and makes it wait for the work
-// queued on ``s`` so far; *h = nullptr when ``s`` belongs to another device
-// than the current one (run everything on ``s`` then).  helper_join makes
-// ``s`` wait for the helper's work and gives the helper back.  0 or TG_EHIP.
-int helper_fork(hipStream_t s, hipStream_t* h);
-int helper_join(hipStream_t h, hipStream_t s);
-void helper_totals(uint64_t* streams, uint64_t* busy);
-
-// Compute units of the current device (grid size of the persistent kernels),
-// looked up once per device.
-inline int device_cus() {
-    // one entry per device, filled by whichever thread gets there first;
-    // every thread would store the same value, but the entries are atomics so
-    // concurrent tg_seal / tg_open calls on one handle are race-free
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int v = cache[dev].load(std::memory_order_relaxed);
-    if (!v) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus <= 0)
-            cus = 256;
-        cache[dev].store(cus, std::memory_order_relaxed);
-        v = cus;
-    }
-    return v;
+// The launchers' AES rounds / direction dispatch: f(integral_constant<int,
+// rounds>, bool_constant<open>) for AES-128 / -256 (10 / 14 rounds);
+// TG_EINVAL for any other ``rounds``.
+template <class F>
+int with_rounds(int rounds, bool open, F&& f) {
+    using R10 = std::integral_constant<int, 10>;
+    using R14 = std::integral_constant<int, 14>;
+    if (rounds == 10) return open ? f(R10{}, std::true_type{}) : f(R10{}, std::false_type{});
+    if (rounds == 14) return open ? f(R14{}, std::true_type{}) : f(R14{}, std::false_type{});
+    return TG_EINVAL;
 }
 
 }  // namespace tg

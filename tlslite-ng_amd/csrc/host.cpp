@@ -217,5 +217,37 @@ int64_t scan_records(const uint8_t* buf, size_t len, uint32_t max_body, uint64_t
     return (int64_t)k;
 }
 
+int hkdf_message(int hashlen, const uint8_t* label, size_t labellen, const uint8_t* ctx, size_t ctxlen,
+                 size_t outlen, HkdfMsg* msg) {
+    if (labellen > 249 || ctxlen > 255) return -1;       // one length byte each
+    if (9 + labellen + 2 + ctxlen > 200) return -1;
+    uint8_t buf[sizeof(msg->words)] = {0};
+    size_t n = 0;
+    buf[n++] = (uint8_t)(outlen >> 8);                   // addTwo(length)
+    buf[n++] = (uint8_t)outlen;
+    buf[n++] = (uint8_t)(6 + labellen);                  // addVarSeq("tls13 " + label, 1, 1)
+    memcpy(buf + n, "tls13 ", 6);
+    n += 6;
+    if (labellen) memcpy(buf + n, label, labellen);
+    n += labellen;
+    buf[n++] = (uint8_t)ctxlen;                          // addVarSeq(hashValue, 1, 1)
+    if (ctxlen) memcpy(buf + n, ctx, ctxlen);
+    n += ctxlen;
+    buf[n++] = 1;                                        // HKDF_expand block counter x = 1
+    buf[n] = 0x80;
+    const size_t block = hashlen == 32 ? 64 : 128, lenfield = hashlen == 32 ? 8 : 16;
+    const uint64_t bits = (uint64_t)(block + n) * 8;     // the (K ^ ipad) block comes first
+    const size_t total = (n + 1 + lenfield + block - 1) / block * block;
+    if (total > sizeof(buf)) return -1;
+    for (int k = 0; k < 8; ++k) buf[total - 1 - k] = (uint8_t)(bits >> (8 * k));
+    memset(msg, 0, sizeof(*msg));
+    msg->nblocks = (uint32_t)(total / block);
+    msg->outlen = (uint32_t)outlen;
+    for (size_t w = 0; w < total / 4; ++w)
+        msg->words[w] = ((uint32_t)buf[4 * w] << 24) | ((uint32_t)buf[4 * w + 1] << 16) |
+                        ((uint32_t)buf[4 * w + 2] << 8) | buf[4 * w + 3];
+    return 0;
+}
+
 }  // namespace host
 }  // namespace tg

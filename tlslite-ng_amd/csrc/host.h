@@ -1,15 +1,25 @@
 // host.h -- the host-only half of libtlsgpu: AES key schedules, the GHASH
-// tables and the record scanner.  Plain C++ (no HIP), built by g++ into the
-// library and, with -fsanitize=address,undefined, into the CPU check
-// tests/native/host_check.cpp (tests/test_host_sanitize.py).
+// tables, the record scanner and the HKDF label packer.  Plain C++ (no HIP),
+// built by g++ into the library and, with -fsanitize=address,undefined, into
+// the CPU check tests/native/host_check.cpp (tests/test_host_sanitize.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 namespace tg {
+
+// The session-independent part of an HKDF-Expand-Label call: HkdfLabel
+// (cryptomath.py:155-173) || 0x01 and its SHA padding, as big-endian 32-bit
+// words of the message blocks that follow the (K ^ ipad) block.
+struct HkdfMsg {
+    uint32_t nblocks;     // SHA-256: 64-byte blocks (16 words); SHA-384: 128-byte (32 words)
+    uint32_t outlen;      // bytes kept of T(1), <= hash length
+    uint32_t words[64];
+};
+
 namespace host {
 
-// Byte image of tg::GcmKeyDev (common.h); api.hip static_asserts that the
+// Byte image of tg::GcmKeyDev (common.h); keys.hip static_asserts that the
 // sizes and member offsets agree.
 struct GcmKeyImage {
     uint32_t rk[60];
@@ -60,6 +70,11 @@ struct ScanError {
 };
 int64_t scan_records(const uint8_t* buf, size_t len, uint32_t max_body, uint64_t* off,
                      uint32_t* rlen, size_t max_n, size_t* consumed, ScanError* err);
+
+// Packs HkdfMsg: 0, or -1 when label and context do not fit
+// (9 + labellen + 2 + ctxlen <= 200).
+int hkdf_message(int hashlen, const uint8_t* label, size_t labellen, const uint8_t* ctx, size_t ctxlen,
+                 size_t outlen, HkdfMsg* msg);
 
 // Parallel host copies (hostcopy.cpp): ``rows`` rows of ``row`` bytes from
 // src + r * src_stride to dst + r * dst_stride, split over up to ``nthreads``

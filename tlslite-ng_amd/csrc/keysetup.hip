@@ -15,7 +15,7 @@
 //                    GCM kernels read (GcmKeyDev / GcmTableKey) or the CCM
 //                    layout (AesKeyDev).
 //   ghash_table_kernel  the 64 KiB single-key GHASH tables from H (the same
-//                    tables api.hip builds on the host).
+//                    tables host.cpp builds on the host).
 #include "aes_bs8.h"
 #include "common.h"
 
@@ -320,7 +320,7 @@ __global__ void aes_setup_kernel(const uint8_t* __restrict__ keys, uint64_t n, v
 }
 
 // M_j[b] = XOR of H * x^(8j + t) over the bits t (MSB first) of b, in the
-// block byte layout (api.hip build_ghash_tables; aesgcm.py:8-14 bit order).
+// block byte layout (host.cpp ghash_tables; aesgcm.py:8-14 bit order).
 // Entry (0, 0) = 0 holds H on entry and is left alone here (every thread reads
 // it); the launcher zeroes it afterwards, stream-ordered.
 
