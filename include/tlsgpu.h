@@ -313,6 +313,65 @@ int tg_hkdf_expand_label(int hashlen, const uint8_t* secrets, uint64_t n, const 
                          uint8_t* out, void* stream);
 int tg_key_create_device(int alg, const uint8_t* keys, size_t keylen, size_t nkeys,
                          tg_key** out, void* stream);
+
+/* Rekeying entries of a LIVE key handle in place: a closed connection's slot
+ * taken by a new one, and TLS 1.3 KeyUpdate (RecordLayer._calcTLS1_3KeyUpdate,
+ * recordlayer.py:1325-1349, calcTLS1_3KeyUpdate_sender / _reciever
+ * :1351-1375).  Both calls are kernels on `stream` and nothing else: no host
+ * synchronisation, no table allocation, no key material copied to the host.
+ * The handle gives the algorithm and key length; every handle type is covered
+ * (AES-GCM tables with their derived arrays, AES-CCM / CCM_8,
+ * ChaCha20-Poly1305, and the single-key AES-GCM handle: nkeys == 1, slot 0,
+ * all of its GHASH tables and key planes).  All arrays are DEVICE pointers.
+ *   slot   n entries, the table rows to rebuild; NULL = rows 0..n-1.  A slot
+ *          that is not below nkeys is skipped: nothing of any table is read
+ *          or written for it (tg_sessions_rekey: its secret, IV and counter
+ *          stay untouched).  The slots of one call must be DISTINCT: with a
+ *          duplicate, the row may end up mixing material of both keys.
+ *   n == 0 is TG_OK with nothing launched; n > nkeys is TG_EINVAL.  Every
+ *   argument error (NULL key / struct / keys / iv_table, bad mode or hashlen,
+ *   nsessions != nkeys, UPDATE without secrets or with new_secrets, INSTALL
+ *   without new_secrets) is reported before any HIP call.
+ * Every byte of a rebuilt row's old material is overwritten (round keys, H,
+ * its powers, the key planes and the rotated round keys).
+ * ORDERING follows `stream` only.  Batches enqueued on `stream` before the
+ * call use the old entries, batches enqueued after it the new ones.  Work on
+ * other streams that uses the handle (or iv_table / secrets / seq_next) must
+ * be ordered against the call by the caller (events), and the caller must
+ * synchronise `stream` before using the host-buffer calls tg_seal / tg_open
+ * on the handle, which run on staging streams of their own.
+ *
+ * tg_key_replace_device: row j of keys (n x keylen bytes) becomes the key of
+ *   entry slot[j].
+ * tg_sessions_rekey: for each selected slot s (list position j), as
+ *   _calcTLS1_3KeyUpdate and calcTLS1_3PendingState (:1291-1316) do:
+ *     TG_REKEY_UPDATE   secret' = HKDF-Expand-Label(secrets[s], "traffic upd",
+ *                       "", hashlen), written back to secrets[s];
+ *     TG_REKEY_INSTALL  secret' = new_secrets[j], copied to secrets[s] when
+ *                       the table is given;
+ *   then key = Expand-Label(secret', "key", "", keylen) rebuilds entry s (the
+ *   raw key exists in registers only), iv_table[s] = Expand-Label(secret',
+ *   "iv", "", 12), and seq_next[s] = 0 when seq_next is given (the fresh
+ *   ConnectionState's seqnum). */
+int tg_key_replace_device(tg_key* k, const uint32_t* slot, const uint8_t* keys,
+                          uint64_t n, void* stream);
+
+#define TG_REKEY_INSTALL 0  /* a new connection takes the slot: secret given */
+#define TG_REKEY_UPDATE  1  /* TLS 1.3 KeyUpdate: the slot's secret advances */
+typedef struct tg_rekey {
+    uint64_t n;
+    uint32_t mode;
+    uint32_t hashlen;           /* 32 (SHA-256) or 48 (SHA-384) */
+    uint64_t nsessions;         /* must equal the handle's nkeys */
+    const uint32_t* slot;       /* n entries; NULL = 0..n-1 */
+    const uint8_t* new_secrets; /* INSTALL: n x hashlen; UPDATE: must be NULL */
+    uint8_t* secrets;           /* nsessions x hashlen table.  UPDATE: required,
+                                   row advanced in place.  INSTALL: optional,
+                                   row overwritten with the new secret */
+    uint8_t* iv_table;          /* nsessions x 12, required */
+    uint64_t* seq_next;         /* optional: counters of the slots set to 0 */
+} tg_rekey;
+int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
 /* Host ingest pipeline (tlsgpu/ingest.py) -- the
  * batched counterpart of RecordSocket (recordlayer.py:35-237).
  * tg_scan_records (HOST memory, no GPU): walk the 5-byte record headers

@@ -517,10 +517,18 @@ int launch_table_wave(const GcmTableKey* keys, uint64_t nkeys, const uint4* hpow
 // The key table's GHASH powers for gcm_table_wave_kernel: one wave per key,
 // lane l ends with H^(l + 1) (normal order); after the step with distance d
 // lanes [0, 2d) hold their powers (H^(l + 1) = H^(l + 1 - d) * H^d).
+// SLOT (rebuilding entries of a live table, keys.hip): the wave at list
+// position j < n does key slot[j], and skips it unless it is below nkeys.
+template <bool SLOT>
 __global__ __launch_bounds__(256) void table_hpow_kernel(const GcmTableKey* __restrict__ keys,
-                                                         uint64_t n, uint4* __restrict__ hpow) {
-    const uint64_t key = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+                                                         uint64_t n, uint4* __restrict__ hpow,
+                                                         const uint32_t* __restrict__ slot, uint64_t nkeys) {
+    uint64_t key = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (key >= n) return;
+    if (SLOT) {
+        key = slot[key];
+        if (key >= nkeys) return;
+    }
     const int lane = threadIdx.x & 63;
     const uint4 h = *reinterpret_cast<const uint4*>(keys[key].hn);
     uint4 p = h;
@@ -589,10 +597,16 @@ bool wave_path(uint64_t n) {
 
 bool tg_gcm_wave_path(uint64_t n) { return tg::wave_path(n); }
 
-int tg_launch_table_hpow(const tg::GcmTableKey* keys, uint64_t n, uint4* hpow, hipStream_t s) {
+int tg_launch_table_hpow(const tg::GcmTableKey* keys, uint64_t n, uint4* hpow, hipStream_t s,
+                         const uint32_t* slot, uint64_t nkeys) {
     const uint64_t groups = (n + 3) / 4;
     if (groups > 0x7fffffffull) return TG_EINVAL;
-    hipLaunchKernelGGL(tg::table_hpow_kernel, dim3((unsigned)groups), dim3(256), 0, s, keys, n, hpow);
+    if (slot)
+        hipLaunchKernelGGL(tg::table_hpow_kernel<true>, dim3((unsigned)groups), dim3(256), 0, s, keys, n, hpow,
+                           slot, nkeys);
+    else
+        hipLaunchKernelGGL(tg::table_hpow_kernel<false>, dim3((unsigned)groups), dim3(256), 0, s, keys, n, hpow,
+                           slot, nkeys);
     return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
 }
 

@@ -1147,11 +1147,19 @@ __global__ __launch_bounds__(1024) void kt_mask_kernel(const GcmTableKey* __rest
 // Per key, the T-table waves' rotated round keys: rot[16 k + r] = rotr8 of
 // round key r (r = 0 .. nr, aes_round.h col_r), rot[16 k + nr + 1] = the
 // plain last round key (t_half reads it after the rotated ones).
-__global__ void kt_rot_kernel(const GcmTableKey* __restrict__ keys, uint64_t n, int nr, uint32_t* __restrict__ rot) {
+// SLOT (rebuilding entries of a live table, keys.hip): list position j < n
+// does key slot[j], and skips it unless it is below nkeys.
+template <bool SLOT>
+__global__ void kt_rot_kernel(const GcmTableKey* __restrict__ keys, uint64_t n, int nr, uint32_t* __restrict__ rot,
+                              const uint32_t* __restrict__ slot, uint64_t nkeys) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t k = t / 64;
+    uint64_t k = t / 64;
     const int e = (int)(t % 64);
     if (k >= n) return;
+    if (SLOT) {
+        k = slot[k];
+        if (k >= nkeys) return;
+    }
     uint32_t w = 0;
     if (e < 4 * (nr + 1))
         w = rotl32(keys[k].rk[e], 24);
@@ -1163,12 +1171,19 @@ __global__ void kt_rot_kernel(const GcmTableKey* __restrict__ keys, uint64_t n, 
 // Per key, the hybrid kernel's key rows (keymath.h bs8_row_word): the
 // MixColumns-folded planes (keymath.h bs8_fold_word) of rounds 1 .. nr - 1 and
 // the round-key planes of rounds 0 and nr, row (8 r + bit) = the four rows' words.
+// SLOT: as kt_rot_kernel.
+template <bool SLOT>
 __global__ void kt_planes_kernel(const GcmTableKey* __restrict__ keys, uint64_t n, int nr,
-                                 uint32_t* __restrict__ planes) {
+                                 uint32_t* __restrict__ planes, const uint32_t* __restrict__ slot,
+                                 uint64_t nkeys) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t k = t / kKtPlaneWords;
+    uint64_t k = t / kKtPlaneWords;
     const int e = (int)(t % kKtPlaneWords);
     if (k >= n) return;
+    if (SLOT) {
+        k = slot[k];
+        if (k >= nkeys) return;
+    }
     const int r = e >> 5, i = (e >> 3) & 3, bit = e & 7;
     const uint32_t w = e >= 32 * (nr + 1) ? 0u
                        : r >= 1 && r < nr ? bs8_fold_word(keys[k].rk, e) : bs8_mask_word(keys[k].rk, e);
@@ -1323,12 +1338,20 @@ int tg_launch_gcm_kt(const tg::GcmTableKey* keys, uint64_t nkeys, const uint4* h
 }
 
 int tg_launch_kt_planes(const tg::GcmTableKey* keys, uint64_t n, int rounds, uint32_t* planes,
-                        uint4* rot, hipStream_t s) {
+                        uint4* rot, hipStream_t s, const uint32_t* slot, uint64_t nkeys) {
     const uint64_t total = n * tg::kKtPlaneWords;
-    hipLaunchKernelGGL(tg::kt_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, keys, n,
-                       rounds, planes);
+    const dim3 pgrid((unsigned)((total + 255) / 256)), rgrid((unsigned)((n * 64 + 255) / 256));
+    if (slot)
+        hipLaunchKernelGGL(tg::kt_planes_kernel<true>, pgrid, dim3(256), 0, s, keys, n, rounds, planes, slot, nkeys);
+    else
+        hipLaunchKernelGGL(tg::kt_planes_kernel<false>, pgrid, dim3(256), 0, s, keys, n, rounds, planes, slot,
+                           nkeys);
     if (hipGetLastError() != hipSuccess) return TG_EHIP;
-    hipLaunchKernelGGL(tg::kt_rot_kernel, dim3((unsigned)((n * 64 + 255) / 256)), dim3(256), 0, s, keys, n,
-                       rounds, reinterpret_cast<uint32_t*>(rot));
+    if (slot)
+        hipLaunchKernelGGL(tg::kt_rot_kernel<true>, rgrid, dim3(256), 0, s, keys, n, rounds,
+                           reinterpret_cast<uint32_t*>(rot), slot, nkeys);
+    else
+        hipLaunchKernelGGL(tg::kt_rot_kernel<false>, rgrid, dim3(256), 0, s, keys, n, rounds,
+                           reinterpret_cast<uint32_t*>(rot), slot, nkeys);
     return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
 }

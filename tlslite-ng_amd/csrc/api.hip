@@ -118,6 +118,40 @@ int tg_hkdf_expand_label(int hashlen, const uint8_t* secrets, uint64_t n, const 
     return rc ? fail(rc, "hkdf launch failed") : TG_OK;
 }
 
+int tg_key_replace_device(tg_key* k, const uint32_t* slot, const uint8_t* keys, uint64_t n, void* stream) {
+    if (!keys && n) return fail(TG_EINVAL, "null keys");   // no rows, nothing to point at
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (n > k->nkeys)
+        return fail(TG_EINVAL, "n (%llu) is above the key handle's nkeys (%llu)", (unsigned long long)n,
+                    (unsigned long long)k->nkeys);
+    if (n == 0) return TG_OK;
+    return tg::key_replace_device(k, slot, keys, n, static_cast<hipStream_t>(stream));
+}
+
+// Argument errors come first, before any HIP call; those of the struct alone
+// are reported whatever the key is.
+int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream) {
+    if (!r) return fail(TG_EINVAL, "null tg_rekey");
+    if (r->mode != TG_REKEY_INSTALL && r->mode != TG_REKEY_UPDATE)
+        return fail(TG_EINVAL, "mode %u is neither TG_REKEY_INSTALL nor TG_REKEY_UPDATE", r->mode);
+    if (r->hashlen != 32 && r->hashlen != 48) return fail(TG_EINVAL, "hashlen must be 32 or 48, got %u", r->hashlen);
+    if (!r->iv_table) return fail(TG_EINVAL, "null iv_table");
+    if (r->mode == TG_REKEY_UPDATE && !r->secrets)
+        return fail(TG_EINVAL, "TG_REKEY_UPDATE needs the secrets table");
+    if (r->mode == TG_REKEY_UPDATE && r->new_secrets)
+        return fail(TG_EINVAL, "TG_REKEY_UPDATE takes no new_secrets");
+    if (r->mode == TG_REKEY_INSTALL && !r->new_secrets) return fail(TG_EINVAL, "TG_REKEY_INSTALL needs new_secrets");
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (r->nsessions != k->nkeys)
+        return fail(TG_EINVAL, "nsessions (%llu) must equal the key handle's nkeys (%llu)",
+                    (unsigned long long)r->nsessions, (unsigned long long)k->nkeys);
+    if (r->n > k->nkeys)
+        return fail(TG_EINVAL, "n (%llu) is above the key handle's nkeys (%llu)", (unsigned long long)r->n,
+                    (unsigned long long)k->nkeys);
+    if (r->n == 0) return TG_OK;
+    return tg::sessions_rekey(k, *r, static_cast<hipStream_t>(stream));
+}
+
 int tg_key_destroy(tg_key* k) {
     if (k) tg::key_destroy(k);
     return TG_OK;

@@ -342,7 +342,10 @@ int tg_launch_gcm_hy(const tg::GcmKeyDev* key, int rounds, const tg_batch& b, bo
 int tg_launch_gcm_bs8(const tg::GcmKeyDev* key, int rounds, const tg_batch& b, bool open,
                       hipStream_t s, const uint32_t* order);
 // hpow[64 k + e - 1] = H_k^e (normal order), e = 1..64, for the n keys.
-int tg_launch_table_hpow(const tg::GcmTableKey* keys, uint64_t n, uint4* hpow, hipStream_t s);
+// slot (both derive launchers): NULL, or n device entries -- list position j
+// then rebuilds key slot[j] of a live table, skipped unless below nkeys.
+int tg_launch_table_hpow(const tg::GcmTableKey* keys, uint64_t n, uint4* hpow, hipStream_t s,
+                         const uint32_t* slot = nullptr, uint64_t nkeys = 0);
 int tg_length_order(const uint32_t* len, uint64_t n, uint32_t* order, void* scratch, size_t* bytes,
                     hipStream_t s);
 // Open over a key table: zero the output of every record whose key_idx is not
@@ -381,7 +384,7 @@ int tg_launch_gcm_table_wave(const tg::GcmTableKey* keys, uint64_t nkeys, const 
 // The key table's bitsliced key rows (planes) and the T-table waves' rotated
 // round keys (rot, 16 x 16 bytes per key).
 int tg_launch_kt_planes(const tg::GcmTableKey* keys, uint64_t n, int rounds, uint32_t* planes,
-                        uint4* rot, hipStream_t s);
+                        uint4* rot, hipStream_t s, const uint32_t* slot = nullptr, uint64_t nkeys = 0);
 int tg_launch_ccm(const tg::AesKeyDev* keys, uint64_t nkeys, int rounds, int taglen,
                   const tg_batch& b, bool open, hipStream_t s);
 // Whether a single-key batch of n records runs the wave-per-record kernel
@@ -409,6 +412,17 @@ int tg_launch_hkdf(int hashlen, const tg::HkdfMsg& msg, const uint8_t* secrets, 
                    uint8_t* out, hipStream_t s);
 int tg_launch_aes_setup(int keylen, int layout, const uint8_t* keys, uint64_t n, void* out,
                         hipStream_t s);
+// Rebuilds entries of a live key allocation (keysetup.hip rekey_kernel):
+// lane j does entry slot[j] (NULL: j), skipped unless below nkeys.  hashlen 0:
+// the raw keys are the rows of src.  hashlen 32 / 48 (msgs: the "traffic
+// upd", "key" and "iv" HkdfMsg): TLS 1.3 install (src = the new secrets) or
+// KeyUpdate (src NULL, row of ``secrets`` advanced in place).  layout 0 / 1 /
+// 2 as tg_launch_aes_setup (0 runs the single key's chain too; 1 leaves the
+// table's derived arrays to the slot forms of the derive launchers), 3 =
+// ChachaKeyDev.
+int tg_launch_rekey(int hashlen, int keylen, int layout, const tg::HkdfMsg* msgs, const uint32_t* slot,
+                    const uint8_t* src, uint8_t* secrets, uint8_t* iv_table, uint64_t* seq_next, uint64_t n,
+                    uint64_t nkeys, void* out, hipStream_t s);
 int tg_launch_gather(const uint8_t* src, const uint64_t* src_off, const uint32_t* len, uint8_t* dst,
                      const uint64_t* dst_off, uint64_t n, hipStream_t s);
 int tg_launch_nonces(int mode, const uint8_t* iv_host, uint64_t seq0, uint64_t n, uint8_t* out,

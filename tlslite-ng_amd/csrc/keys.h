@@ -73,5 +73,9 @@ inline uint4* table_rot(const tg_key* k) {
 int key_create(int alg, const uint8_t* keys, size_t keylen, size_t nkeys, tg_key** out);
 int key_create_device(int alg, const uint8_t* keys, size_t keylen, size_t nkeys, tg_key** out, hipStream_t st);
 void key_destroy(tg_key* k);
+// tg_key_replace_device / tg_sessions_rekey behind their argument checks:
+// entries of the live allocation rebuilt by kernels on ``st`` alone.
+int key_replace_device(tg_key* k, const uint32_t* slot, const uint8_t* keys, uint64_t n, hipStream_t st);
+int sessions_rekey(tg_key* k, const tg_rekey& r, hipStream_t st);
 
 }  // namespace tg

@@ -205,6 +205,44 @@ int key_create_device(int alg, const uint8_t* keys, size_t keylen, size_t nkeys,
     return hand_over(k, rc, out);
 }
 
+namespace {
+
+// Entries of a live allocation rebuilt on ``st``: the fused front kernel, then
+// (AES-GCM table) the slot forms of the derive kernels over the same list.
+// No allocation, no copy to the host and no synchronisation.
+int rebuild(tg_key* k, int hashlen, const HkdfMsg* msgs, const uint32_t* slot, const uint8_t* src,
+            uint8_t* secrets, uint8_t* iv_table, uint64_t* seq_next, uint64_t n, hipStream_t st) {
+    const int layout = k->alg == TG_CHACHA20_POLY1305 ? 3 : is_ccm(k->alg) ? 2 : (k->nkeys > 1 ? 1 : 0);
+    int rc = tg_launch_rekey(hashlen, (int)k->keylen, layout, msgs, slot, src, secrets, iv_table, seq_next, n,
+                             k->nkeys, k->dev_key, st);
+    if (!rc && layout == 1) {
+        const auto* keys = static_cast<const GcmTableKey*>(k->dev_key);
+        rc = tg_launch_table_hpow(keys, n, table_hpow(k), st, slot, k->nkeys);
+        if (!rc) rc = tg_launch_kt_planes(keys, n, k->rounds, table_planes(k), table_rot(k), st, slot, k->nkeys);
+    }
+    return rc ? fail(rc, "rekey launch failed: %s", hipGetErrorString(hipGetLastError())) : TG_OK;
+}
+
+}  // namespace
+
+int key_replace_device(tg_key* k, const uint32_t* slot, const uint8_t* keys, uint64_t n, hipStream_t st) {
+    int rc = select_device(k);
+    if (rc) return rc;
+    return rebuild(k, 0, nullptr, slot, keys, nullptr, nullptr, nullptr, n, st);
+}
+
+int sessions_rekey(tg_key* k, const tg_rekey& r, hipStream_t st) {
+    HkdfMsg msgs[3];
+    const size_t h = r.hashlen;
+    if (host::hkdf_message((int)h, (const uint8_t*)"traffic upd", 11, nullptr, 0, h, &msgs[0]) ||
+        host::hkdf_message((int)h, (const uint8_t*)"key", 3, nullptr, 0, k->keylen, &msgs[1]) ||
+        host::hkdf_message((int)h, (const uint8_t*)"iv", 2, nullptr, 0, 12, &msgs[2]))
+        return fail(TG_EINVAL, "label too long");
+    int rc = select_device(k);
+    if (rc) return rc;
+    return rebuild(k, (int)h, msgs, r.slot, r.new_secrets, r.secrets, r.iv_table, r.seq_next, r.n, st);
+}
+
 void key_destroy(tg_key* k) {
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess && cur != k->device) (void)hipSetDevice(k->device);

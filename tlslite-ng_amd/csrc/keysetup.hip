@@ -16,6 +16,11 @@
 //                    layout (AesKeyDev).
 //   ghash_table_kernel  the 64 KiB single-key GHASH tables from H (the same
 //                    tables host.cpp builds on the host).
+//   rekey_kernel     entries of a LIVE key allocation rebuilt in place, from
+//                    raw keys or through the TLS 1.3 derivation (install /
+//                    KeyUpdate), fused: HKDF, key expansion, H and the
+//                    entry's store in one lane (tg_key_replace_device,
+//                    tg_sessions_rekey).
 #include "aes_bs8.h"
 #include "common.h"
 
@@ -135,21 +140,17 @@ __device__ __forceinline__ typename H::word load_be(const uint8_t* p) {
     }
 }
 
-// HMAC(secret, info || 0x01) truncated to outlen: HKDF_expand's first block
-// T(1) (cryptomath.py:146-153), which is all of it for outlen <= hash length.
+// HMAC(secret, info || 0x01): HKDF_expand's first block T(1)
+// (cryptomath.py:146-153), which is all of it for outlen <= hash length.
+// key: the secret as big-endian words, zero-padded to one hash block; st
+// receives the digest words.
 template <class H>
-__global__ __launch_bounds__(256) void hkdf_kernel(tg::HkdfMsg msg, const uint8_t* __restrict__ secrets, uint64_t n,
-                            uint8_t* __restrict__ out) {
+__device__ __forceinline__ void hkdf_t1(const tg::HkdfMsg& msg, const typename H::word key[16],
+                                        typename H::word st[8]) {
     using W = typename H::word;
     constexpr int WB = sizeof(W);
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint8_t* sec = secrets + (uint64_t)H::kHash * i;
-    W key[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) key[k] = k * WB < H::kHash ? load_be<H>(sec + k * WB) : W(0);
     const W ipad = (W)0x3636363636363636ull, opad = (W)0x5c5c5c5c5c5c5c5cull;
-    W st[8], blk[16];
+    W blk[16];
     // inner: H((K ^ ipad) || info || 0x01)
     H::init(st);
 #pragma unroll
@@ -180,6 +181,21 @@ __global__ __launch_bounds__(256) void hkdf_kernel(tg::HkdfMsg msg, const uint8_
     blk[dw] = (W)1 << (8 * WB - 1);                        // 0x80 terminator
     blk[15] = (W)((16 * WB + H::kHash) * 8);               // bit length of block + digest
     H::compress(st, blk);
+}
+
+template <class H>
+__global__ __launch_bounds__(256) void hkdf_kernel(tg::HkdfMsg msg, const uint8_t* __restrict__ secrets, uint64_t n,
+                            uint8_t* __restrict__ out) {
+    using W = typename H::word;
+    constexpr int WB = sizeof(W);
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* sec = secrets + (uint64_t)H::kHash * i;
+    W key[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) key[k] = k * WB < H::kHash ? load_be<H>(sec + k * WB) : W(0);
+    W st[8];
+    hkdf_t1<H>(msg, key, st);
     uint8_t* o = out + (uint64_t)msg.outlen * i;
     for (uint32_t k = 0; k < msg.outlen; ++k) {
         const W wv = st[k / WB];
@@ -225,13 +241,10 @@ __device__ __forceinline__ uint32_t sub_word(const uint8_t* sb, uint32_t w) {
 
 // FIPS-197 key expansion (rijndael.py:922-993); words are LE words of the
 // key-schedule bytes (the layout every AES kernel reads).
+// expand_words: rk[0 .. NK) hold the key already.
 template <int NK>
-__device__ __forceinline__ void expand_key(const uint8_t* sb, const uint8_t* key, uint32_t rk[60]) {
+__device__ __forceinline__ void expand_words(const uint8_t* sb, uint32_t rk[60]) {
     constexpr int NR = NK + 6, TOTAL = 4 * (NR + 1);
-#pragma unroll
-    for (int k = 0; k < NK; ++k)
-        rk[k] = (uint32_t)key[4 * k] | ((uint32_t)key[4 * k + 1] << 8) |
-                ((uint32_t)key[4 * k + 2] << 16) | ((uint32_t)key[4 * k + 3] << 24);
     uint32_t rcon = 1;
 #pragma unroll
     for (int k = NK; k < TOTAL; ++k) {
@@ -246,6 +259,15 @@ __device__ __forceinline__ void expand_key(const uint8_t* sb, const uint8_t* key
     }
 #pragma unroll
     for (int k = TOTAL; k < 60; ++k) rk[k] = 0;
+}
+
+template <int NK>
+__device__ __forceinline__ void expand_key(const uint8_t* sb, const uint8_t* key, uint32_t rk[60]) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+        rk[k] = (uint32_t)key[4 * k] | ((uint32_t)key[4 * k + 1] << 8) |
+                ((uint32_t)key[4 * k + 2] << 16) | ((uint32_t)key[4 * k + 3] << 24);
+    expand_words<NK>(sb, rk);
 }
 
 // E_K(0^128) bytewise (SubBytes, ShiftRows, MixColumns) -> H as 4 LE words.
@@ -282,16 +304,12 @@ __device__ __forceinline__ void aes_zero_block(const uint8_t* sb, const uint32_t
 }
 
 // out layouts: 0 = GcmKeyDev (single key), 1 = GcmTableKey[n], 2 = AesKeyDev[n]
+// Entry i of ``out`` from its expanded schedule: every byte of the entry is
+// written (layout 0: rk, rounds, pad and H parked in ghash[0]; the rest of a
+// GcmKeyDev is the launcher's chain).
 template <int NK, int LAYOUT>
-__global__ void aes_setup_kernel(const uint8_t* __restrict__ keys, uint64_t n, void* out) {
-    __shared__ uint8_t sb[256];
-    for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void store_aes_entry(const uint8_t* sb, const uint32_t rk[60], void* out, uint64_t i) {
     constexpr int NR = NK + 6;
-    uint32_t rk[60];
-    expand_key<NK>(sb, keys + 4 * NK * i, rk);
     if (LAYOUT == 2) {
         AesKeyDev* o = static_cast<AesKeyDev*>(out) + i;
 #pragma unroll
@@ -319,12 +337,155 @@ __global__ void aes_setup_kernel(const uint8_t* __restrict__ keys, uint64_t n, v
     o->ghash[0] = make_uint4(h[0], h[1], h[2], h[3]);   // H parked in entry (0, 0), see below
 }
 
+template <int NK, int LAYOUT>
+__global__ void aes_setup_kernel(const uint8_t* __restrict__ keys, uint64_t n, void* out) {
+    __shared__ uint8_t sb[256];
+    for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t rk[60];
+    expand_key<NK>(sb, keys + 4 * NK * i, rk);
+    store_aes_entry<NK, LAYOUT>(sb, rk, out, i);
+}
+
+// ------------------------------------------------------- rekey in place --
+// tg_key_replace_device / tg_sessions_rekey: lane j rebuilds entry slot[j]
+// of a live key table (slot NULL: entry j); a slot that is not below nkeys is
+// skipped, nothing read or written for it.
+//   H = NoHash      the new raw key is row j of ``src`` (tg_key_replace_device)
+//   H = Sha256/384  TLS 1.3 (recordlayer.py:1291-1316, :1325-1349): the
+//       slot's secret is row j of ``src`` (install; copied to row s of
+//       ``secrets`` when that is given) or row s of ``secrets`` advanced with
+//       "traffic upd" and written back (update, src NULL); key and IV are
+//       Expand-Label(secret, "key" / "iv"), the IV goes to row s of iv_table,
+//       seq_next[s] = 0.  The raw key lives in registers only.
+// NK = 4 / 8: AES-128 / -256 into layout 0 / 1 / 2 (aes_setup_kernel's);
+// NK = 0: ChaCha20-Poly1305, the 32 key bytes as ChachaKeyDev (layout 3).
+struct NoHash {
+    using word = uint32_t;
+    static constexpr int kHash = 0;
+};
+
+struct RekeyMsgs {
+    tg::HkdfMsg upd, key, iv;
+};
+
+typedef uint32_t u32_u1 __attribute__((aligned(1)));
+
+__device__ __forceinline__ uint32_t load_u32u(const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(1))) u32_u1*)p;
+#else
+    return 0;
+#endif
+}
+__device__ __forceinline__ void store_u32u(uint8_t* p, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(__attribute__((address_space(1))) u32_u1*)p = v;
+#endif
+}
+
+// The digest as big-endian 32-bit words of its bytes.
+template <class H>
+__device__ __forceinline__ void digest_words(const typename H::word st[8], uint32_t d[12]) {
+    if constexpr (sizeof(typename H::word) == 4) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d[k] = st[k];
+#pragma unroll
+        for (int k = 8; k < 12; ++k) d[k] = 0;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            d[2 * k] = (uint32_t)(st[k] >> 32);
+            d[2 * k + 1] = (uint32_t)st[k];
+        }
+    }
+}
+
+template <class H, int NK, int LAYOUT>
+__global__ __launch_bounds__(256) void rekey_kernel(RekeyMsgs msgs, const uint32_t* __restrict__ slot,
+                                                    const uint8_t* __restrict__ src, uint8_t* __restrict__ secrets,
+                                                    uint8_t* __restrict__ iv_table, uint64_t* __restrict__ seq_next,
+                                                    uint64_t n, uint64_t nkeys, void* out) {
+    constexpr int KW = NK ? NK : 8;   // key words
+    __shared__ uint8_t sb[256];
+    if (NK) {
+        for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
+        __syncthreads();
+    }
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t s = slot ? (uint64_t)slot[j] : j;
+    if (s >= nkeys) return;
+    uint32_t rk[60];   // rk[0 .. KW): the key as LE words of its bytes
+    if constexpr (H::kHash == 0) {
+#pragma unroll
+        for (int k = 0; k < KW; ++k) rk[k] = load_u32u(src + 4 * KW * j + 4 * k);
+    } else {
+        using W = typename H::word;
+        constexpr int WB = sizeof(W), HW = H::kHash / 4;   // secret as 32-bit words
+        const uint8_t* from = src ? src + (uint64_t)H::kHash * j : secrets + (uint64_t)H::kHash * s;
+        W sec[16], st[8];
+        uint32_t d[12];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k * WB >= H::kHash) {
+                sec[k] = W(0);
+            } else if constexpr (WB == 4) {
+                sec[k] = bswap32(load_u32u(from + 4 * k));
+            } else {
+                sec[k] = ((uint64_t)bswap32(load_u32u(from + 8 * k)) << 32) | bswap32(load_u32u(from + 8 * k + 4));
+            }
+        }
+        if (!src) {   // KeyUpdate: the secret advances (uniform branch)
+            hkdf_t1<H>(msgs.upd, sec, st);
+#pragma unroll
+            for (int k = 0; k < H::kStateOut; ++k) sec[k] = st[k];
+        }
+        if (secrets) {
+            uint8_t* to = secrets + (uint64_t)H::kHash * s;
+            digest_words<H>(sec, d);
+#pragma unroll
+            for (int k = 0; k < HW; ++k) store_u32u(to + 4 * k, bswap32(d[k]));
+        }
+        hkdf_t1<H>(msgs.iv, sec, st);
+        digest_words<H>(st, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store_u32u(iv_table + 12 * s + 4 * k, bswap32(d[k]));
+        hkdf_t1<H>(msgs.key, sec, st);
+        digest_words<H>(st, d);
+#pragma unroll
+        for (int k = 0; k < KW; ++k) rk[k] = bswap32(d[k]);
+        if (seq_next) seq_next[s] = 0;
+    }
+    if constexpr (NK == 0) {
+        ChachaKeyDev* o = static_cast<ChachaKeyDev*>(out) + s;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o->k[k] = rk[k];
+    } else {
+        expand_words<NK>(sb, rk);
+        store_aes_entry<NK, LAYOUT>(sb, rk, out, s);
+    }
+}
+
 // M_j[b] = XOR of H * x^(8j + t) over the bits t (MSB first) of b, in the
 // block byte layout (host.cpp ghash_tables; aesgcm.py:8-14 bit order).
 // Entry (0, 0) = 0 holds H on entry and is left alone here (every thread reads
 // it); the launcher zeroes it afterwards, stream-ordered.
+//
+// The five kernels of this chain also rebuild a live single-key handle
+// (rekey_kernel, layout 0).  GUARD: the rebuild's one-entry slot list; when it
+// names another entry than 0 rekey_kernel wrote nothing, so the chain leaves
+// the key alone too.  Key creation runs them with GUARD false.
+template <bool GUARD>
+__device__ __forceinline__ bool slot_skipped(const uint32_t* slot) {
+    return GUARD && slot && *slot != 0;
+}
 
-__global__ void ghash_table_kernel(GcmKeyDev* key) {
+template <bool GUARD>
+__global__ void ghash_table_kernel(GcmKeyDev* key, const uint32_t* slot) {
+    if (slot_skipped<GUARD>(slot)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;   // entry j * 256 + b
     if (e == 0 || e >= kGhashEntries) return;
     const uint4 hw = key->ghash[0];                         // H as LE words of its bytes
@@ -333,7 +494,9 @@ __global__ void ghash_table_kernel(GcmKeyDev* key) {
 }
 
 // GcmKeyDev::ghash64: the same tables for H^64 (after hpow_kernel).
-__global__ void ghash64_table_kernel(GcmKeyDev* key) {
+template <bool GUARD>
+__global__ void ghash64_table_kernel(GcmKeyDev* key, const uint32_t* slot) {
+    if (slot_skipped<GUARD>(slot)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= kGhashEntries) return;
     const uint4 p = key->hpow[63];                          // normal order -> byte layout
@@ -343,7 +506,9 @@ __global__ void ghash64_table_kernel(GcmKeyDev* key) {
 }
 
 // GcmKeyDev::ghash8: the same tables for H^8 (after hpow_kernel).
-__global__ void ghash8_table_kernel(GcmKeyDev* key) {
+template <bool GUARD>
+__global__ void ghash8_table_kernel(GcmKeyDev* key, const uint32_t* slot) {
+    if (slot_skipped<GUARD>(slot)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= kGhashEntries) return;
     const uint4 p = key->hpow[7];
@@ -355,7 +520,9 @@ __global__ void ghash8_table_kernel(GcmKeyDev* key) {
 // GcmKeyDev::hpow: thread e computes H^(e+1) by square and multiply from H,
 // which aes_setup_kernel parked in ghash[0] (the table kernel leaves entry 0
 // alone and the launcher zeroes it after this kernel, stream-ordered).
-__global__ void hpow_kernel(GcmKeyDev* key) {
+template <bool GUARD>
+__global__ void hpow_kernel(GcmKeyDev* key, const uint32_t* slot) {
+    if (slot_skipped<GUARD>(slot)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= kHPow) return;
     const uint4 hw = key->ghash[0];
@@ -371,12 +538,31 @@ __global__ void hpow_kernel(GcmKeyDev* key) {
 
 // GcmKeyDev::bs8mask from the round keys (after aes_setup_kernel, layout 0):
 // 32 (NR + 1) <= 480 planes.
-__global__ void bs_mask_kernel(GcmKeyDev* key) {
+template <bool GUARD>
+__global__ void bs_mask_kernel(GcmKeyDev* key, const uint32_t* slot) {
+    if (slot_skipped<GUARD>(slot)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int nr = (int)key->rounds;
     if (e < 32 * (nr + 1)) key->bs8mask[e] = bs8::mask_word(key->rk, e);
     if (e < 15 * 32) key->bs8rows[e] = bs8_row_word(key->rk, nr, e);   // the hybrid's key rows
     if (e < 64) key->rkrot[e] = rkrot_word(key->rk, nr, e);
+    // the rebuild's last kernel un-parks H itself (creation: the launcher's memset)
+    if (GUARD && e == 0) key->ghash[0] = make_uint4(0, 0, 0, 0);
+}
+
+// Everything of a GcmKeyDev behind rk and H (parked in ghash[0]).
+template <bool GUARD>
+int launch_single_chain(GcmKeyDev* k, const uint32_t* slot, hipStream_t s) {
+    hipLaunchKernelGGL(ghash_table_kernel<GUARD>, dim3(kGhashEntries / 256), dim3(256), 0, s, k, slot);
+    if (hipGetLastError() != hipSuccess) return TG_EHIP;
+    hipLaunchKernelGGL(hpow_kernel<GUARD>, dim3((kHPow + 255) / 256), dim3(256), 0, s, k, slot);
+    if (hipGetLastError() != hipSuccess) return TG_EHIP;
+    hipLaunchKernelGGL(ghash64_table_kernel<GUARD>, dim3(kGhashEntries / 256), dim3(256), 0, s, k, slot);
+    if (hipGetLastError() != hipSuccess) return TG_EHIP;
+    hipLaunchKernelGGL(ghash8_table_kernel<GUARD>, dim3(kGhashEntries / 256), dim3(256), 0, s, k, slot);
+    if (hipGetLastError() != hipSuccess) return TG_EHIP;
+    hipLaunchKernelGGL(bs_mask_kernel<GUARD>, dim3((15 * 32 + 255) / 256), dim3(256), 0, s, k, slot);
+    return hipGetLastError() == hipSuccess ? TG_OK : TG_EHIP;
 }
 
 }  // namespace
@@ -417,17 +603,49 @@ int tg_launch_aes_setup(int keylen, int layout, const uint8_t* keys, uint64_t n,
     if (hipGetLastError() != hipSuccess) return TG_EHIP;
     if (layout == 0) {
         tg::GcmKeyDev* k = static_cast<tg::GcmKeyDev*>(out);
-        hipLaunchKernelGGL(tg::ghash_table_kernel, dim3(tg::kGhashEntries / 256), dim3(256), 0, s, k);
-        if (hipGetLastError() != hipSuccess) return TG_EHIP;
-        hipLaunchKernelGGL(tg::hpow_kernel, dim3((tg::kHPow + 255) / 256), dim3(256), 0, s, k);
-        if (hipGetLastError() != hipSuccess) return TG_EHIP;
-        hipLaunchKernelGGL(tg::ghash64_table_kernel, dim3(tg::kGhashEntries / 256), dim3(256), 0, s, k);
-        if (hipGetLastError() != hipSuccess) return TG_EHIP;
-        hipLaunchKernelGGL(tg::ghash8_table_kernel, dim3(tg::kGhashEntries / 256), dim3(256), 0, s, k);
-        if (hipGetLastError() != hipSuccess) return TG_EHIP;
-        hipLaunchKernelGGL(tg::bs_mask_kernel, dim3((15 * 32 + 255) / 256), dim3(256), 0, s, k);
-        if (hipGetLastError() != hipSuccess) return TG_EHIP;
+        if (int rc = tg::launch_single_chain<false>(k, nullptr, s)) return rc;
         if (hipMemsetAsync(&k->ghash[0], 0, sizeof(uint4), s) != hipSuccess) return TG_EHIP;
     }
+    return TG_OK;
+}
+
+int tg_launch_rekey(int hashlen, int alg_keylen, int layout, const tg::HkdfMsg* msgs, const uint32_t* slot,
+                    const uint8_t* src, uint8_t* secrets, uint8_t* iv_table, uint64_t* seq_next, uint64_t n,
+                    uint64_t nkeys, void* out, hipStream_t s) {
+    using namespace tg;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    RekeyMsgs m{};
+    if (hashlen) {
+        m.upd = msgs[0];
+        m.key = msgs[1];
+        m.iv = msgs[2];
+    }
+#define TG_REKEY(H, NK, L)                                                                          \
+    hipLaunchKernelGGL((rekey_kernel<H, NK, L>), dim3(blocks), dim3(256), 0, s, m, slot, src, secrets, \
+                       iv_table, seq_next, n, nkeys, out)
+#define TG_REKEY_HASH(NK, L)                  \
+    do {                                      \
+        if (hashlen == 0) TG_REKEY(NoHash, NK, L);      \
+        else if (hashlen == 32) TG_REKEY(Sha256, NK, L); \
+        else if (hashlen == 48) TG_REKEY(Sha384, NK, L); \
+        else return TG_EINVAL;                \
+    } while (0)
+    if (layout == 3) {   // ChaCha20-Poly1305
+        TG_REKEY_HASH(0, 3);
+    } else if (alg_keylen == 16) {
+        if (layout == 0) TG_REKEY_HASH(4, 0);
+        else if (layout == 1) TG_REKEY_HASH(4, 1);
+        else TG_REKEY_HASH(4, 2);
+    } else if (alg_keylen == 32) {
+        if (layout == 0) TG_REKEY_HASH(8, 0);
+        else if (layout == 1) TG_REKEY_HASH(8, 1);
+        else TG_REKEY_HASH(8, 2);
+    } else {
+        return TG_EINVAL;
+    }
+#undef TG_REKEY_HASH
+#undef TG_REKEY
+    if (hipGetLastError() != hipSuccess) return TG_EHIP;
+    if (layout == 0) return launch_single_chain<true>(static_cast<GcmKeyDev*>(out), slot, s);
     return TG_OK;
 }

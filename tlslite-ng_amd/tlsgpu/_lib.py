@@ -33,7 +33,11 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_hkdf_expand_label", "tg_key_create_device", "tg_scan_records", "tg_gather",
            "tg_selftest_poly1305", "tg_selftest_ghash", "tg_set_option", "tg_get_option",
            "tg_scratch_info", "tg_scratch_trim", "tg_helper_info", "tg_host_copy", "tg_host_copy_rows",
-           "tg_seal_session_records", "tg_open_session_records")
+           "tg_seal_session_records", "tg_open_session_records", "tg_key_replace_device",
+           "tg_sessions_rekey")
+
+TG_REKEY_INSTALL = 0
+TG_REKEY_UPDATE = 1
 
 TG_TLS12 = 0x0303
 TG_TLS13 = 0x0304
@@ -112,6 +116,21 @@ class TgSessionRecords(ctypes.Structure):
     ]
 
 
+class TgRekey(ctypes.Structure):
+    """``struct tg_rekey`` (include/tlsgpu.h)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("mode", ctypes.c_uint32),
+        ("hashlen", ctypes.c_uint32),
+        ("nsessions", ctypes.c_uint64),
+        ("slot", ctypes.c_void_p),
+        ("new_secrets", ctypes.c_void_p),
+        ("secrets", ctypes.c_void_p),
+        ("iv_table", ctypes.c_void_p),
+        ("seq_next", ctypes.c_void_p),
+    ]
+
+
 class TlsGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libtlsgpu error %d: %s" % (code, msg))
@@ -176,6 +195,9 @@ def load():
     if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_seal_session_records"):
         l.tg_seal_session_records.argtypes = [p, ctypes.POINTER(TgSessionRecords), p]
         l.tg_open_session_records.argtypes = [p, ctypes.POINTER(TgSessionRecords), p]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_sessions_rekey"):
+        l.tg_key_replace_device.argtypes = [p, p, p, u64, p]
+        l.tg_sessions_rekey.argtypes = [p, ctypes.POINTER(TgRekey), p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):

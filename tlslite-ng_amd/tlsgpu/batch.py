@@ -76,6 +76,49 @@ class KeyTable(object):
                              keylen=t.keylen, stream=_stream(stream))
         return t
 
+    def replace(self, slots, keys, stream=None):
+        """Give entries of the live table new keys, in place
+        (tg_key_replace_device): row j of ``keys`` (n x key length device
+        bytes, or a list of keys) becomes the key of entry ``slots[j]``
+        (``None``: entries 0..n-1).  Stream-ordered and asynchronous: batches
+        enqueued on ``stream`` before the call use the old keys, batches after
+        it the new ones.  Slots must be distinct; one that is not below
+        ``nkeys`` is skipped."""
+        if not hasattr(keys, "data_ptr") and not isinstance(keys, int):
+            import numpy as np
+            import torch
+            raw = b"".join(bytes(k) for k in keys)
+            if len(raw) % self.keylen:
+                raise ValueError("keys must be %d bytes each" % self.keylen)
+            keys = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).cuda()
+        slots, n = _slot_list(slots, None if isinstance(keys, int) else keys.numel() // self.keylen)
+        if not isinstance(keys, int) and keys.numel() != n * self.keylen:
+            raise ValueError("keys must hold one %d-byte row per slot" % self.keylen)
+        self._rekey_args = (slots, keys)   # alive until the next call at least
+        dk = self._dkey
+        _lib.check(dk._lib.tg_key_replace_device(dk.handle, _ptr(slots, "slots"), _ptr(keys, "keys"), n,
+                                                 _stream(stream)))
+
+
+def _slot_list(slots, default_n):
+    """``(device uint32 array or None, n)`` of a slot argument: ``None`` (the
+    first ``default_n`` entries), a device int32 / uint32 tensor, or host
+    integers below 2^32 (uploaded)."""
+    if slots is None:
+        if default_n is None:
+            raise ValueError("slots=None needs the row count")
+        return None, int(default_n)
+    if hasattr(slots, "data_ptr"):
+        if slots.element_size() != 4 or slots.dtype.is_floating_point:
+            raise ValueError("slots must be a 32-bit integer tensor")
+        return slots, slots.numel()
+    import numpy as np
+    import torch
+    a = np.asarray(list(slots), dtype=np.uint64)
+    if a.size and int(a.max()) >= 2 ** 32:
+        raise ValueError("slots must be below 2^32")
+    return torch.from_numpy(a.astype(np.uint32).view(np.int32)).cuda(), int(a.size)
+
 
 def _handle(key):
     if isinstance(key, _HipAEAD):

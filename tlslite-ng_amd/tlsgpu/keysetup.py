@@ -11,6 +11,9 @@ sessions in one launch:
   HBM (``tg_key_create_device``);
 * ``key_update``         -- the "traffic upd" step of a TLS 1.3 KeyUpdate.
 
+These build new arrays and a new table.  A live ``tlsgpu.Sessions`` is updated in
+place instead (``Sessions.key_update`` / ``install``, ``tg_sessions_rekey``).
+
 Secrets, keys and IVs are device tensors (uint8, one row per session).
 """
 from . import _lib

@@ -8,17 +8,28 @@ of the sessions (tg_seal_session_records / tg_open_session_records in counter
 mode): each session's records are numbered in batch order and its counter
 advances, as ``getSeqNumBytes`` does per record.
 
+The state is live: ``key_update`` advances chosen sessions as a TLS 1.3
+KeyUpdate does (``_calcTLS1_3KeyUpdate``, recordlayer.py:1325-1349) and
+``install`` hands a slot to a new connection, both in place and ordered on
+the stream only (tg_sessions_rekey).
+
 This is the thin state holder only; gathering records from many sockets is
 the caller's business.
 """
-from . import keysetup, records
-from .batch import KeyTable
+import ctypes
+
+from . import _lib, keysetup, records
+from .batch import KeyTable, _ptr, _slot_list, _stream
 
 
 class Sessions(object):
-    def __init__(self, table, ivs, version=records.TLS13, seq_next=None):
+    def __init__(self, table, ivs, version=records.TLS13, seq_next=None, secrets=None,
+                 cipher_suite=None):
         """``table``: a KeyTable; ``ivs``: device uint8 tensor, one row (4 or
-        12 bytes) per key; ``seq_next``: device int64 counters (default 0)."""
+        12 bytes) per key; ``seq_next``: device int64 counters (default 0);
+        ``secrets`` / ``cipher_suite``: the TLS 1.3 traffic secrets the table
+        was derived from (device uint8, one row per key) and their suite --
+        what ``key_update`` advances."""
         import torch
         if not isinstance(table, KeyTable):
             raise TypeError("table must be a KeyTable")
@@ -29,15 +40,26 @@ class Sessions(object):
         elif seq_next.numel() != table.nkeys or seq_next.dtype != torch.int64:
             raise ValueError("seq_next must hold one int64 counter per key of the table")
         self.table, self.ivs, self.version, self.seq_next = table, ivs, int(version), seq_next
+        self.cipher_suite = cipher_suite
+        self.hashlen = keysetup.TLS13_SUITES[cipher_suite][2] if cipher_suite is not None else None
+        if secrets is not None:
+            if self.hashlen is None:
+                raise ValueError("secrets need their cipher_suite")
+            if secrets.numel() != table.nkeys * self.hashlen:
+                raise ValueError("secrets must have one %d-byte row per key of the table" % self.hashlen)
+        self.secrets = secrets
 
     @classmethod
     def from_traffic_secrets(cls, cipher_suite, secrets, stream=None):
         """One direction of many TLS 1.3 sessions from their traffic secrets
         (n x hash length device bytes), as calcTLS1_3PendingState derives key
         and IV (recordlayer.py:1291-1312); counters start at 0.  Keys, IVs and
-        the key table never leave device memory."""
+        the key table never leave device memory.  A device copy of the secrets
+        stays with the object (``secrets``) for ``key_update``."""
         table, _, ivs = keysetup.traffic_keys(cipher_suite, secrets, stream=stream)
-        return cls(table, ivs, records.TLS13)
+        hashlen = keysetup.TLS13_SUITES[cipher_suite][2]
+        return cls(table, ivs, records.TLS13, secrets=secrets.reshape(-1, hashlen).clone(),
+                   cipher_suite=cipher_suite)
 
     def __len__(self):
         return self.table.nkeys
@@ -45,6 +67,44 @@ class Sessions(object):
     def seq(self):
         """The per-session sequence counters (device int64 tensor)."""
         return self.seq_next
+
+    def _rekey(self, mode, slots, new_secrets, n, stream):
+        if self.version != records.TLS13 or self.ivs.shape[1] != 12:
+            raise ValueError("rekeying derives TLS 1.3 keys and 12-byte IVs")
+        r = _lib.TgRekey()
+        r.n, r.mode, r.hashlen, r.nsessions = n, mode, self.hashlen, self.table.nkeys
+        r.slot = _ptr(slots, "slots")
+        r.new_secrets = _ptr(new_secrets, "secrets")
+        r.secrets = _ptr(self.secrets, "secrets")
+        r.iv_table = _ptr(self.ivs, "ivs")
+        r.seq_next = _ptr(self.seq_next, "seq_next")
+        self._rekey_args = (slots, new_secrets)   # alive until the next call at least
+        dk = self.table._dkey
+        _lib.check(dk._lib.tg_sessions_rekey(dk.handle, ctypes.byref(r), _stream(stream)))
+
+    def key_update(self, slots, stream=None):
+        """TLS 1.3 KeyUpdate of the sessions ``slots`` (distinct; a device
+        int32 tensor, host integers, or ``None`` for all): the secret advances
+        with "traffic upd", key-table entry and IV are re-derived from it and
+        the sequence counter restarts at 0, as calcTLS1_3KeyUpdate_sender /
+        _reciever install a fresh ConnectionState (recordlayer.py:1351-1375).
+        In place and ordered on ``stream`` only: batches enqueued before the
+        call use the old keys, batches after it the new ones."""
+        if self.secrets is None:
+            raise ValueError("these Sessions were built without traffic secrets: nothing to advance")
+        slots, n = _slot_list(slots, self.table.nkeys)
+        self._rekey(_lib.TG_REKEY_UPDATE, slots, None, n, stream)
+
+    def install(self, slots, secrets, stream=None):
+        """New connections take the sessions ``slots``: row j of ``secrets``
+        (n x hash length device bytes) is the traffic secret of ``slots[j]``;
+        key, IV and counter as ``from_traffic_secrets`` gives a new session."""
+        if self.hashlen is None:
+            raise ValueError("these Sessions have no cipher_suite: the PRF hash is unknown")
+        slots, n = _slot_list(slots, secrets.numel() // self.hashlen)
+        if secrets.numel() != n * self.hashlen:
+            raise ValueError("secrets must hold one %d-byte row per slot" % self.hashlen)
+        self._rekey(_lib.TG_REKEY_INSTALL, slots, secrets, n, stream)
 
     def seal(self, session, n, data, data_off, data_len, ctype, wire, wire_off, wire_len,
              pad_len=None, seq_out=None, stream=None):
