@@ -372,6 +372,86 @@ typedef struct tg_rekey {
     uint64_t* seq_next;         /* optional: counters of the slots set to 0 */
 } tg_rekey;
 int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
+
+/* TLS 1.1 / 1.2 AES-CBC + HMAC records -- the block-cipher suites of
+ * RecordLayer._getCipherSettings / _getMacSettings (recordlayer.py:1056-1063,
+ * :1087-1095): AES-128 / AES-256 in CBC mode with HMAC-SHA1 / -SHA256 /
+ * -SHA384, MAC-then-encrypt (_macThenEncrypt :476-498, _decryptThenMAC
+ * :680-719 with ct_check_cbc_mac_and_pad, constanttime.py:102-204) and
+ * encrypt-then-MAC, RFC 7366 (_encryptThenMAC :500-520, _macThenDecrypt
+ * :721-778).  One connection direction per call: one cipher key, one MAC key,
+ * record i has sequence number seq0 + i.  The MAC input is calculateMAC's
+ * (:463-474): be64(seq) || type || version(2) || be16(len) || bytes.
+ *
+ * The key is a handle type of its own (the AEAD handles and their algorithm
+ * switches are untouched).  It holds the round keys, the round keys of the
+ * equivalent inverse cipher and the two HMAC midstates, built at creation and
+ * scrubbed at destroy.  mackeylen is 1 .. the hash's block size (64, SHA-384:
+ * 128).  tg_cbc_key_destroy waits for the device first.
+ *
+ * All arrays of tg_cbc_records are DEVICE pointers; calls are ordered on
+ * `stream`.  Every argument error (NULL key or struct, a version other than
+ * TG_TLS11 / TG_TLS12, etm > 1, seal without iv, bad key lengths, unknown
+ * mac) is TG_EINVAL before any HIP call; n == 0 is TG_OK with nothing
+ * launched.
+ *   seal: fragment data + data_off[i], data_len[i] bytes (read only; at most
+ *         2^14, so that the body fits the header's 16-bit length), content
+ *         type ctype[i], explicit IV iv + 16 i (for TLS >= 1.1 the reference
+ *         sends a random block first; its ciphertext is this IV).  Writes
+ *         header || iv || CBC(data || MAC || padding)        (etm == 0)
+ *         header || iv || CBC(data || padding) || MAC        (etm == 1)
+ *         at wire + wire_off[i] with the reference's minimal padding
+ *         (addPadding :453-461) and its size to wire_len[i]:
+ *         5 + 16 + roundup16(len + D + 1), or 5 + 16 + roundup16(len + 1) + D,
+ *         D = 20 / 32 / 48.
+ *   open: wire record (header included) at wire + wire_off[i], wire_len[i]
+ *         bytes.  Plaintext goes to data + data_off[i] (room for
+ *         wire_len[i] - 21 bytes), its length to data_len[i], the header's
+ *         type to ctype[i] and to status[i] the code of what recvRecord
+ *         raises for the record, in the reference's order of checks:
+ *         TG_REC_OVERFLOW (header length over recv_limit + 2048, or plaintext
+ *         over recv_limit), TG_REC_DECRYPT_FAILED, TG_REC_BAD_MAC (every
+ *         TLSBadRecordMAC: MAC mismatch, bad padding, too short, nothing left
+ *         after the IV), TG_REC_OK.  Under etm the MAC is checked before the
+ *         block-multiple test.  For any status but TG_REC_OK data_len[i] = 0
+ *         and every byte written to the record's data extent is zero again.
+ *         MAC-then-encrypt costs the same hash blocks and AES blocks whatever
+ *         the decrypted bytes are (it depends on wire_len[i] and the MAC).
+ * Nothing outside a record's own data and wire extents is written.  Any
+ * alignment is accepted; data_off[i] and wire_off[i] + 5 at 16-byte
+ * alignment take the vector path. */
+#define TG_TLS11 0x0302
+#define TG_MAC_SHA1 1
+#define TG_MAC_SHA256 2
+#define TG_MAC_SHA384 3
+#define TG_REC_DECRYPT_FAILED 9 /* TLSDecryptionFailed: body not a multiple of 16 */
+
+typedef struct tg_cbc_key tg_cbc_key;
+int tg_cbc_key_create(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_key,
+                      size_t mackeylen, int mac, tg_cbc_key** out);
+int tg_cbc_key_destroy(tg_cbc_key* k);
+
+typedef struct tg_cbc_records {
+    uint64_t n;
+    uint32_t version;           /* TG_TLS11 or TG_TLS12 */
+    uint32_t etm;               /* 0 = MAC-then-encrypt, 1 = encrypt-then-MAC */
+    uint32_t recv_limit;        /* open: recv_record_limit (0 = 2^14) */
+    uint32_t reserved;          /* the alignment hole in front of seq0, named; ignored */
+    uint64_t seq0;
+    uint8_t* data;
+    const uint64_t* data_off;
+    uint32_t* data_len;
+    uint8_t* ctype;
+    const uint8_t* iv;          /* seal: n x 16 bytes */
+    uint8_t* wire;
+    const uint64_t* wire_off;
+    uint32_t* wire_len;
+    uint8_t* status;            /* open */
+} tg_cbc_records;
+
+int tg_cbc_seal_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
+int tg_cbc_open_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
+
 /* Host ingest pipeline (tlsgpu/ingest.py) -- the
  * batched counterpart of RecordSocket (recordlayer.py:35-237).
  * tg_scan_records (HOST memory, no GPU): walk the 5-byte record headers

@@ -11,9 +11,11 @@ from .aead import HipAESCCM, HipAESGCM, HipCHACHA20_POLY1305  # noqa: F401
 from .batch import KeyTable, make_batch, make_nonces, open_batch, seal_batch  # noqa: F401
 from .cipherfactory import (CIPHER_IMPLEMENTATIONS, createAESCCM, createAESCCM_8,  # noqa: F401
                             createAESGCM, createCHACHA20)
-from .records import (TLS12, TLS13, open_records, open_session_records, seal_records,  # noqa: F401
+from .records import (TLS11, TLS12, TLS13, open_records, open_session_records, seal_records,  # noqa: F401
                       seal_session_records)
 from . import keysetup  # noqa: F401
+from . import cbc  # noqa: F401
+from .cbc import CbcKey  # noqa: F401
 from .sessions import Sessions  # noqa: F401
 from .ingest import RecordReader, RecordWriter  # noqa: F401
 

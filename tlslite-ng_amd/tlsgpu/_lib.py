@@ -34,17 +34,24 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_selftest_poly1305", "tg_selftest_ghash", "tg_set_option", "tg_get_option",
            "tg_scratch_info", "tg_scratch_trim", "tg_helper_info", "tg_host_copy", "tg_host_copy_rows",
            "tg_seal_session_records", "tg_open_session_records", "tg_key_replace_device",
-           "tg_sessions_rekey")
+           "tg_sessions_rekey", "tg_cbc_key_create", "tg_cbc_key_destroy", "tg_cbc_seal_records",
+           "tg_cbc_open_records")
 
 TG_REKEY_INSTALL = 0
 TG_REKEY_UPDATE = 1
 
+TG_TLS11 = 0x0302
 TG_TLS12 = 0x0303
 TG_TLS13 = 0x0304
+# HMAC of a CBC key (tg_cbc_key_create)
+TG_MAC_SHA1 = 1
+TG_MAC_SHA256 = 2
+TG_MAC_SHA384 = 3
+TG_REC_DECRYPT_FAILED = 9
 # per-record status of tg_open_records (include/tlsgpu.h TG_REC_*)
 REC_STATUS = {0: "ok", 1: "bad_record_mac", 2: "truncated", 3: "length_mismatch",
               4: "unexpected_content_type", 5: "illegal_version", 6: "no_content_type",
-              7: "record_overflow", 8: "bad_session"}
+              7: "record_overflow", 8: "bad_session", 9: "decryption_failed"}
 
 
 class TgBatch(ctypes.Structure):
@@ -131,6 +138,27 @@ class TgRekey(ctypes.Structure):
     ]
 
 
+class TgCbcRecords(ctypes.Structure):
+    """``struct tg_cbc_records`` (include/tlsgpu.h)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("version", ctypes.c_uint32),
+        ("etm", ctypes.c_uint32),
+        ("recv_limit", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("seq0", ctypes.c_uint64),
+        ("data", ctypes.c_void_p),
+        ("data_off", ctypes.c_void_p),
+        ("data_len", ctypes.c_void_p),
+        ("ctype", ctypes.c_void_p),
+        ("iv", ctypes.c_void_p),
+        ("wire", ctypes.c_void_p),
+        ("wire_off", ctypes.c_void_p),
+        ("wire_len", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 class TlsGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libtlsgpu error %d: %s" % (code, msg))
@@ -198,6 +226,11 @@ def load():
     if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_sessions_rekey"):
         l.tg_key_replace_device.argtypes = [p, p, p, u64, p]
         l.tg_sessions_rekey.argtypes = [p, ctypes.POINTER(TgRekey), p]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_cbc_key_create"):
+        l.tg_cbc_key_create.argtypes = [p, sz, p, sz, i, ctypes.POINTER(ctypes.c_void_p)]
+        l.tg_cbc_key_destroy.argtypes = [p]
+        l.tg_cbc_seal_records.argtypes = [p, ctypes.POINTER(TgCbcRecords), p]
+        l.tg_cbc_open_records.argtypes = [p, ctypes.POINTER(TgCbcRecords), p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):

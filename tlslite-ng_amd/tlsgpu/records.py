@@ -26,6 +26,7 @@ import ctypes
 from . import _lib
 from .batch import _handle, _ptr, _stream
 
+TLS11 = _lib.TG_TLS11
 TLS12 = _lib.TG_TLS12
 TLS13 = _lib.TG_TLS13
 STATUS = _lib.REC_STATUS
