@@ -43,14 +43,18 @@ TG_BS_HD uint32_t bop3(uint32_t a, uint32_t b, uint32_t c, uint32_t tt) {
 #endif
 TG_BS_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return bop3(a, b, c, 0x96); }
 
-// v_perm_b32: byte i of the result = byte sel_i of (hi:lo) (0..3 = lo, 4..7 = hi).
+// v_perm_b32: byte i of the result = byte sel_i of (hi:lo) (0..3 = lo, 4..7 = hi;
+// 0x0c = a zero byte).
 TG_BS_HD uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_perm(hi, lo, sel);
 #else
     const uint64_t v = ((uint64_t)hi << 32) | lo;
     uint32_t r = 0;
-    for (int i = 0; i < 4; ++i) r |= (uint32_t)((v >> (8 * ((sel >> (8 * i)) & 7))) & 0xff) << (8 * i);
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t k = (sel >> (8 * i)) & 0xff;
+        if (k < 8) r |= (uint32_t)((v >> (8 * k)) & 0xff) << (8 * i);
+    }
     return r;
 #endif
 }

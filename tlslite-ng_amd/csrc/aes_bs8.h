@@ -417,12 +417,13 @@ struct RoundRows<KM, decltype((void)KM::kRound)> {
 template <class KM>
 TG_BS_HD constexpr bool round_rows() { return RoundRows<KM>::value; }
 
-template <int NR, class KM>
-TG_BS_HD void encrypt(uint32_t (*s)[8], const KM& km, uint32_t (*w)[8], bool sub01 = true) {
+// Round 1 on the state after AddRoundKey 0 (peeled off the rolled loop: its
+// S-box of rows 0-1 is optional, see above).
+template <class KM>
+TG_BS_HD void round1(uint32_t (*s)[8], const KM& km, bool sub01 = true) {
     // KeyPlanesVec: the round's key rows are fetched before its S-box gates
     Word4 c[8];
     if constexpr (round_rows<KM>()) km.round(1, c);
-    // round 1 peeled off the rolled loop: its S-box of rows 0-1 is optional
     if (sub01) {
         bs::sbox(s[0]);
         TG_BS8_FENCE();
@@ -439,10 +440,17 @@ TG_BS_HD void encrypt(uint32_t (*s)[8], const KM& km, uint32_t (*w)[8], bool sub
         mix_round_folded(s, km, 1);
     else
         mix_round(s, km, 1);
+}
+
+// Rounds r0 .. NR on the state after round r0 - 1 (r0 = 2 after round1, 3
+// after the window path's win_rounds); w receives the blocks (to_blocks).
+template <int NR, class KM>
+TG_BS_HD void rounds_from(uint32_t (*s)[8], const KM& km, uint32_t (*w)[8], int r0) {
+    Word4 c[8];
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
 #endif
-    for (int r = 2; r < NR; ++r) {
+    for (int r = r0; r < NR; ++r) {
         if constexpr (round_rows<KM>()) km.round(r, c);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -462,6 +470,149 @@ TG_BS_HD void encrypt(uint32_t (*s)[8], const KM& km, uint32_t (*w)[8], bool sub
         TG_BS8_FENCE();
     }
     to_blocks(s, w);
+}
+
+template <int NR, class KM>
+TG_BS_HD void encrypt(uint32_t (*s)[8], const KM& km, uint32_t (*w)[8], bool sub01 = true) {
+    round1(s, km, sub01);
+    rounds_from<NR>(s, km, w, 2);
+}
+
+// ---- 256-counter windows: rounds 1-2 from per-(record, window) constants ----
+// With counters below 2^16 only byte 15 of the counter block (row 3, column
+// 3) differs between the blocks of a window of 256 counters (ctr >> 8 fixed),
+// and byte 14 between windows.  ShiftRows moves row 3 of column 3 to column 0,
+// so after round 1 only column 0 depends on the block:
+//   state1[:, 0] = A ^ (1,1,3,2) . S[low8(ctr) ^ rk0[15]]
+// and after round 2 every column c is a constant plus MixColumns' share of the
+// one byte ShiftRows brings it from column 0 (row r = (4 - c) % 4):
+//   state2[:, c] = B[:, c] ^ M[:, r] . (S(state1[r, 0]) ^ 0x63).
+// A depends on the record (nonce bytes 0, 5, 10), B on the record and the
+// window.  The lane's eight blocks have the counters 2 + rho + 64 beta + 8 j,
+// so the byte-15 term is one of 32 per-key values V[rho][beta % 4] (bit j of
+// each byte = block j; block 7 of rho >= 6, beta % 4 = 3 wraps into the next
+// window with the right low byte, and takes that window's B: win_sel7).
+// Rounds 1-2 are then 8 XORs, ONE S-box call on column 0 packed into one
+// register set (byte r = row r), the 2x / 3x planes and a byte scatter,
+// instead of six S-box calls and two MixColumns.  The same function as
+// encrypt() (an algebraic regrouping of rijndael.py:995-1038), checked
+// against it and the oracle on the CPU (tests/native/bs8_win_check.cpp).
+
+// S-box of the four bytes of w; sb(x) = S[x] (device: the LDS table).
+template <class SB>
+TG_BS_HD uint32_t sub4(uint32_t w, const SB& sb) {
+    return sb(w & 0xffu) | (sb((w >> 8) & 0xffu) << 8) | (sb((w >> 16) & 0xffu) << 16) | (sb(w >> 24) << 24);
+}
+
+// MixColumns of one column packed as a LE word (byte i = row i).
+TG_BS_HD uint32_t mix_col(uint32_t w) {
+    const uint32_t r1 = rotr_bytes(w, 1), r2 = rotr_bytes(w, 2), r3 = rotr_bytes(w, 3);
+    const uint32_t u = w ^ r1;
+    const uint32_t xt = ((u & 0x7f7f7f7fu) << 1) ^ (((u >> 7) & 0x01010101u) * 0x1bu);
+    return xt ^ xor3(r1, r2, r3);
+}
+
+// Column c after ShiftRows: row i from column (c + i) % 4 (columns = LE words).
+TG_BS_HD uint32_t shift_col(const uint32_t s[4], int c) {
+    return (s[c] & 0x000000ffu) | (s[(c + 1) & 3] & 0x0000ff00u) | (s[(c + 2) & 3] & 0x00ff0000u) |
+           (s[(c + 3) & 3] & 0xff000000u);
+}
+
+// A (column 0 after round 1 without the byte-15 term, LE word: byte r = row r)
+// and B (the four columns after round 2 with column 0's S-box outputs taken
+// as 0x63, i.e. the circuit's zero; round key 2 included) of the record with
+// nonce words n0..n2 for window ``win`` = ctr >> 8.  rk: the schedule words.
+template <class SB>
+TG_BS_HD void win_words(const uint32_t* rk, uint32_t n0, uint32_t n1, uint32_t n2, uint32_t win, const SB& sb,
+                        uint32_t& A, uint32_t (&B)[4]) {
+    // bytes 12..14 of the block = bytes 3..1 of be32(win << 8); byte 15 left zero
+    const uint32_t cw = ((win >> 16) & 0xffu) | (win & 0xff00u) | ((win & 0xffu) << 16);
+    const uint32_t s[4] = {n0 ^ rk[0], n1 ^ rk[1], n2 ^ rk[2], cw ^ rk[3]};
+    uint32_t a[4];
+    A = mix_col(sub4(shift_col(s, 0), sb) & 0x00ffffffu) ^ rk[4];
+    a[0] = 0;   // S[0] = 0x63: what round 2 takes from column 0 is added by win_rounds
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 1; c < 4; ++c) a[c] = mix_col(sub4(shift_col(s, c), sb)) ^ rk[4 + c];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 0; c < 4; ++c) B[c] = mix_col(sub4(shift_col(a, c), sb)) ^ rk[8 + c];
+}
+
+// Plane b of A for win_rounds: byte r = 0x00 / 0xff from bit b of row r.
+TG_BS_HD uint32_t a_plane(uint32_t A, uint32_t b) { return ((A >> b) & 0x01010101u) * 0xffu; }
+// Plane e = 8 i + b of B (row i, bit b; byte c = column c) is rec_plane(B, e).
+
+// Word b of V[rho][bm] (bm = beta % 4): byte r, bit j = bit b of
+// (1,1,3,2)_r . S[low8(2 + rho + 8 j + 64 bm) ^ k15], k15 = byte 15 of round
+// key 0.  256 words per key.
+template <class SB>
+TG_BS_HD uint32_t v_word(uint32_t k15, uint32_t rho, uint32_t bm, uint32_t b, const SB& sb) {
+    uint32_t w = 0;
+    for (uint32_t j = 0; j < 8; ++j) {
+        const uint32_t s = sb(((2u + rho + 8u * j + 64u * bm) & 0xffu) ^ k15);
+        const uint32_t s2 = ((s << 1) ^ ((s & 0x80u) ? 0x11bu : 0u)) & 0xffu;
+        const uint32_t col = s | (s << 8) | ((s2 ^ s) << 16) | (s2 << 24);
+        w |= ((col >> b) & 0x01010101u) << j;
+    }
+    return w;
+}
+
+// The full-round fallback's state after AddRoundKey 0 (batches the window
+// path does not take: counters from 2^16 on), built on demand from u (nonce
+// words ^ round key 0, rec_plane) and the lane's first counter c0 of batch 0.
+TG_BS_HD void first_state(const uint32_t u[4], uint32_t c0, uint32_t beta, bool hi, uint32_t (*s)[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int e = 0; e < 32; ++e) s[e >> 3][e & 7] = rec_plane(u, e);
+    uint32_t lanec[6], kmask;
+    lane_consts<3>(c0, lanec, kmask);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < 6; ++b) s[3][b] ^= lanec[b];
+    ctr_planes<6, 16, 6>(s, kmask, beta);
+    if (hi) ctr_planes<16, 32, 6>(s, kmask, beta);
+}
+
+// Block 7 of a lane with kmask (lane_consts) lies in the next window when
+// beta % 4 = 3: its bit of every byte takes the next window's B plane.
+TG_BS_HD uint32_t win_m7(uint32_t kmask) { return kmask & 0x80808080u; }
+TG_BS_HD uint32_t win_sel7(uint32_t cur, uint32_t next, uint32_t m7) { return bop3(m7, next, cur, 0xca); }
+
+// Rounds 1-2.  x[b] = A plane b ^ V[rho][beta % 4] word b (column 0 after
+// round 1); bp(b) = the B planes of bit b, rows 0..3 (one ds_read_b128 in
+// the kernel, read after the S-box so that they are not live across it); s
+// receives the state after round 2 (rounds_from<NR>(s, km, w, 3) follows).
+template <class BP>
+TG_BS_HD void win_rounds(uint32_t (&x)[8], const BP& bp, uint32_t (*s)[8]) {
+    bs::sbox(x);   // y = S(column 0) ^ 0x63, byte r = row r
+    TG_BS8_FENCE();
+    // ShiftRows sends row r of column 0 to column (4 - r) % 4, where row i
+    // gets M[i][r] y_r.  Every row takes 1 . y of two columns, so with
+    // z = (y_0, y_3, y_2, y_1) row i is z ^ e_i ^ B_i, e_i holding 3 y where
+    // the coefficient is 2 and 2 y where it is 3:
+    //   row 0 (2 y0,   y3,   y2, 3 y1)    row 1 (  y0,   y3, 3 y2, 2 y1)
+    //   row 2 (  y0, 3 y3, 2 y2,   y1)    row 3 (3 y0, 2 y3,   y2,   y1)
+    // 2 y on planes: bit b <- bit b - 1, bit 7 fed back into bits 0, 1, 3, 4.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int b = 0; b < 8; ++b) {
+        const uint32_t p = x[(b + 7) & 7];   // bit b - 1
+        const uint32_t y2 = b == 0 ? p : (b == 1 || b == 3 || b == 4) ? p ^ x[7] : p;
+        const uint32_t y3 = b == 0 ? p ^ x[0] : (b == 1 || b == 3 || b == 4) ? xor3(p, x[7], x[b]) : p ^ x[b];
+        const uint32_t z = perm(x[b], x[b], 0x01020300u);
+        const Word4 k = bp(b);
+        s[0][b] = xor3(z, perm(y3, y2, 0x010c0c04u), k.x);
+        s[1][b] = xor3(z, perm(y3, y2, 0x05020c0cu), k.y);
+        s[2][b] = xor3(z, perm(y3, y2, 0x0c06030cu), k.z);
+        s[3][b] = xor3(z, perm(y3, y2, 0x0c0c0700u), k.w);
+        TG_BS8_FENCE();
+    }
 }
 
 }  // namespace bs8

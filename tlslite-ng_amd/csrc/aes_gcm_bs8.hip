@@ -41,7 +41,7 @@
 namespace tg {
 namespace {
 
-// Per-wave LDS of octet_job: the first-state planes of each record (128 B per
+// Per-wave LDS of octet_job without WIN: the first-state planes of each record (128 B per
 // record slot, up to 8) at recw, and round 1's S-box output of their rows 0
 // and 1 (64 B per slot) at recw + 1024.
 constexpr uint32_t kRecArea = 1536;
@@ -58,6 +58,41 @@ constexpr size_t kBs8Lds = kBs8RecBase + (kBs8Threads / 64) * kRecArea;
 // No static __shared__ in this file: the GHASH tables sit at LDS address 0
 // (gmul's absolute addresses).
 extern __shared__ __attribute__((aligned(16))) uint4 g_lds_bs8[];
+
+// S-box providers of the window path's builders (aes_bs8.h win_words, v_word).
+struct SboxLds {   // the 256-byte table in LDS (stage_sbox)
+    uint32_t base;
+    __device__ __forceinline__ uint32_t operator()(uint32_t x) const { return lds_u8(base + x); }
+};
+// The B planes of bit b for bs8::win_rounds: rows 0..3 in one ds_read_b128
+// from the current window's buffer; in a crossing batch (wave-uniform) bit 7
+// of the lanes with m7 from the next window's.
+struct WinPlanes {
+    uint32_t cur, nxt, m7;
+    bool cross;
+    __device__ __forceinline__ uint4 operator()(int b) const {
+        uint4 v = lds_u128(cur + 128u * b);
+        if (cross) {
+            const uint4 n = lds_u128(nxt + 128u * b);
+            v = make_uint4(bs8::win_sel7(v.x, n.x, m7), bs8::win_sel7(v.y, n.y, m7), bs8::win_sel7(v.z, n.z, m7),
+                           bs8::win_sel7(v.w, n.w, m7));
+        }
+        return v;
+    }
+};
+struct SboxTe {    // byte 1 of Te0[x]
+    __device__ __forceinline__ uint32_t operator()(uint32_t x) const { return (c_te.te0[x] >> 8) & 0xffu; }
+};
+
+// The key's V table (aes_bs8.h v_word), 1 KiB at LDS ``base``: word k of half
+// h of V[rho][bm] at 256 bm + 128 h + 16 rho + 4 k, so the octets' lanes (one
+// rho each) read 128 consecutive bytes per ds_read_b128.  Threads 0..255.
+__device__ __forceinline__ void stage_vtab(uint32_t base, uint32_t k15) {
+    const uint32_t e = threadIdx.x;
+    if (e < 256)
+        reinterpret_cast<uint32_t*>(g_lds_bs8)[base / 4 + e] =
+            bs8::v_word(k15, (e >> 2) & 7u, e >> 6, 4u * ((e >> 5) & 1u) + (e & 3u), SboxTe());
+}
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
@@ -123,7 +158,8 @@ struct RoleProbe {
 // The T-table keystream of half h of a lane's batch: counters c0 + 8 j,
 // j = 4 h .. 4 h + 3, in lock step (one round-key read per round for the four), through
 // the 256-counter window cache (aes_round.h) when no lane of the wave crosses
-// a window in this batch (a wave-uniform test), else full rounds.  Round keys
+// a window in this batch (a wave-uniform test), else full rounds (WLDS, below:
+// always the window cache).  Round keys
 // are read from LDS (wave-uniform address: one broadcast ds_read_b128 per
 // round), which keeps the 44 / 60 key words out of the SGPR file.
 // The hybrid kernel's T-table columns of rounds 2 .. NR - 1 take the round keys
@@ -133,20 +169,26 @@ struct RoleProbe {
 
 // LPR: the lanes per record of the job -- a lane's blocks are LPR apart (8:
 // the single-key hybrid's octets; 32: the key-table hybrid's pairs).
-template <int NR, int LPR = 8, class RK = RkLds>
+// WLDS (the single-key hybrid's octets): the window constants are read from
+// the wave's LDS slots, ``wcur`` for the batch's window and ``w7`` for block 7
+// of the batch (h = 1, q = 3) -- the next window's slot on a lane whose block
+// 7 crosses into it, else wcur -- so every batch takes the window path.
+template <int NR, int LPR = 8, class RK = RkLds, bool WLDS = false>
 __device__ __forceinline__ void t_half(uint32_t lane4, const RK& rk, const CtrCache& cc,
-                                       uint32_t c0, bool win, const uint4& wc, uint32_t k0w, int h,
-                                       uint4 (&ks)[4]) {
+                                       uint32_t c0, bool win, const uint4& wc0, uint32_t k0w, int h,
+                                       uint4 (&ks)[4], uint32_t wcur = 0, uint32_t w7 = 0) {
     uint32_t s[4][4];
+    const uint4 wc = WLDS ? lds_u128(wcur) : wc0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const uint32_t ctr = c0 + (uint32_t)LPR * (4 * h + q);
-        if (win) {   // rounds 1-2 from the window constants (aes_ctr_win)
+        if (WLDS || win) {   // rounds 1-2 from the window constants (aes_ctr_win)
+            const uint4 wq = WLDS && q == 3 ? lds_u128(h ? w7 : wcur) : wc;
             const uint32_t A = cc.k0 ^ rotl32(T2<3>((ctr << 24) ^ k0w, lane4), 8);
-            s[q][0] = wc.x ^ T0<0>(A, lane4);
-            s[q][1] = wc.y ^ rotl32(T2<3>(A, lane4), 8);
-            s[q][2] = wc.z ^ T2<2>(A, lane4);
-            s[q][3] = wc.w ^ rotl32(T0<1>(A, lane4), 8);
+            s[q][0] = wq.x ^ T0<0>(A, lane4);
+            s[q][1] = wq.y ^ rotl32(T2<3>(A, lane4), 8);
+            s[q][2] = wq.z ^ T2<2>(A, lane4);
+            s[q][3] = wq.w ^ rotl32(T0<1>(A, lane4), 8);
         } else {     // round 1 from the record cache, then round 2 (aes_ctr_w)
             const uint32_t s3 = bswap32(ctr) ^ k0w;
             const uint32_t a0 = cc.k0 ^ rotl32(T2<3>(s3, lane4), 8);
@@ -249,14 +291,20 @@ struct TableKeyCtx {    // a key of a key table: the wave's 4-bit H^8 tables in 
 // kc.gmul multiplies by H^LPR), batch beta of the lane holds its blocks
 // rho + LPR (8 beta + j), j = 0..7, so each load / store instruction still
 // moves LPR x 16 consecutive bytes per record (whole 128-byte lines).
+// WIN (the single-key hybrid's bitsliced waves): rounds 1-2 of the bitsliced
+// cipher from the 256-counter window constants; ``recw`` is then the wave's
+// window area (kHyBsArea, or kHyBsArea1 with one B buffer: ``dbl`` false) and
+// ``vtab`` the key's V table in LDS (stage_vtab).
 template <int NR, bool OPEN, bool TROLE, class KM, class KC, bool PRE = false, int LPR = 8,
-          class RKT = RkLds>
+          class RKT = RkLds, bool WIN = false>
 __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
                                           const uint32_t* __restrict__ order, uint64_t t0,
                                           uint32_t recw, const RKT& rkT, uint32_t sbox,
-                                          const KM& km, uint32_t tid = threadIdx.x) {
+                                          const KM& km, uint32_t tid = threadIdx.x, uint32_t vtab = 0,
+                                          bool dbl = false) {
     static_assert(LPR == 8 || LPR == 16 || LPR == 32 || LPR == 64, "lanes per record");
     static_assert(LPR == 8 || LPR == 32 || !TROLE, "the T-table role runs octets or pairs");
+    static_assert(!WIN || LPR == 8, "the window areas: octets");
     constexpr uint32_t kM = LPR - 1, kS = LPR == 8 ? 3 : LPR == 16 ? 4 : LPR == 32 ? 5 : 6;
     const uint32_t* rk = kc.rk();
     // payload loads and stores with the non-temporal hint: read or written
@@ -301,7 +349,7 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
     CtrCache cc = {0, 0, 0, 0};
     if (TROLE) {
         cc = ctr_cache<NR>(lane4, rkT, nv);
-    } else {   // the record's first-state planes 4 l .. 4 l + 3 (nonce ^ rk0 spread to bytes)
+    } else if constexpr (!WIN) {   // the record's first-state planes 4 l .. 4 l + 3 (nonce ^ rk0 spread to bytes)
         const uint32_t u[4] = {nv.x ^ rk[0], nv.y ^ rk[1], nv.z ^ rk[2], rk[3]};
         const uint32_t e = 4 * (l & 7u);
         const uint4 rp = make_uint4(bs8::rec_plane(u, e), bs8::rec_plane(u, e + 1),
@@ -330,6 +378,9 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
     // per-slot precomputed keystream blocks: E_K(J0) at 2 t, the last block's
     // at 2 t + 1 when the record's last batch holds only that block
     const uint4* mt = kc.masks();
+    // the lane's slot t again, from a fresh lane index: t itself is not held
+    // across the batch loop (two VGPRs; with them the seal kernel spilled)
+    auto slot = [&]() { return t0 + ((fresh_lane() & 63u) >> kS); };
 
     // GHASH over this lane's AAD positions (aesgcm.py:69-79), zero-padded blocks
     uint4 y = make_uint4(0, 0, 0, 0);
@@ -423,7 +474,7 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
 #if defined(TG_DEBUG_ASSERT)
                 assert(lone_last_block<LPR>(nc));
 #endif
-                ks[0] = xor4(gload16(reinterpret_cast<const uint8_t*>(mt + 2 * t + 1)), rkl);
+                ks[0] = xor4(gload16(reinterpret_cast<const uint8_t*>(mt + 2 * slot() + 1)), rkl);
             }
             consume(ks, blk0, 0, std::integral_constant<int, 1>(), nullptr);
         } else if (TROLE) {
@@ -431,9 +482,26 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
             // crosses a window in this batch (wave-uniform); two halves of four.
             // Octets: one window for the batch's counters c0 .. c0 + 56; pairs
             // (LPR 32): a window per half, c0 + 128 h .. c0 + 128 h + 96.
-            const bool win = __all(((c0 ^ (c0 + 7u * LPR)) >> 8) == 0);
+            constexpr bool kTWin = WIN && LPR == 8;
+            const bool win = kTWin || __all(((c0 ^ (c0 + 7u * LPR)) >> 8) == 0);
             const uint32_t k0w = rkT.get(0).w;
-            const uint4 wc = LPR == 8 && win ? win_consts<NR>(lane4, rkT, cc, c0) : make_uint4(0, 0, 0, 0);
+            const uint4 wc = LPR == 8 && win && !kTWin ? win_consts<NR>(lane4, rkT, cc, c0) : make_uint4(0, 0, 0, 0);
+            // WIN: the window constants once per (record, window), in the
+            // wave's LDS area at recw (two buffers of eight records' 16 B;
+            // the octet's lanes all write their record's value).  Window
+            // beta / 4 sits in buffer (beta / 4) % 2; the batch with
+            // beta % 4 = 3 computes the next window's, which block 7 of its
+            // lanes rho >= 6 already takes.
+            uint32_t wcur = 0, w7 = 0;
+            if constexpr (kTWin) {
+                const uint32_t wsl = recw + 16u * (lane >> 3), wnd = beta >> 2;
+                const bool cross = (beta & 3u) == 3u;
+                if (beta == 0) lds_st128(wsl, win_consts<NR>(lane4, rkT, cc, 0u));
+                if (cross) lds_st128(wsl + 128u * ((wnd + 1u) & 1u), win_consts<NR>(lane4, rkT, cc, (wnd + 1u) << 8));
+                __builtin_amdgcn_wave_barrier();
+                wcur = wsl + 128u * (wnd & 1u);
+                w7 = cross && ((c0 >> 3) & 1u) ? wsl + 128u * ((wnd + 1u) & 1u) : wcur;
+            }
 #if defined(TG_T_UNROLL)
 #pragma unroll
 #else
@@ -453,7 +521,7 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
                                     : gload16u(in + 16u * (blk0 + LPR * (4 * h + q)));
                 }
                 if constexpr (LPR == 8) {
-                    t_half<NR>(lane4, rkT, cc, c0, win, wc, k0w, h, ks);
+                    t_half<NR, 8, RKT, kTWin>(lane4, rkT, cc, c0, win, wc, k0w, h, ks, wcur, w7);
                 } else {
                     const uint32_t ch = c0 + 4u * LPR * h;
                     const bool winh = __all(((ch ^ (ch + 3u * LPR)) >> 8) == 0);
@@ -492,24 +560,76 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
                 consume(ks, blk0, 4 * h, std::integral_constant<int, 4>(), nullptr);
             }
         } else {
-            // counters of this batch below 2^16 (wave-uniform): rows 0-1
-            // come in after round 1's SubBytes (bs8::encrypt sub01)
+            // counters of this batch below 2^16 (wave-uniform)
             const bool hi = (beta + 1u) >> (16 - (kS + 3));
             uint32_t s[4][8];
+            bool win = false;
+            if constexpr (WIN) {
+                // Rounds 1-2 from the 256-counter window constants (aes_bs8.h
+                // win_rounds).  The wave's area at recw: the records' A planes
+                // (256 B: half h of record q at 128 h + 16 q), then one or two
+                // (dbl) buffers of B planes (1 KiB: rows 0..3 of bit p of
+                // record q at 128 p + 16 q, so every ds_read_b128 / ds_write_b128
+                // of the wave covers the banks once).  Window beta / 4 sits in
+                // buffer (beta / 4) % 2; the batch with beta % 4 = 3 fills the
+                // other buffer with the next window's, which block 7 of its
+                // lanes rho >= 6 already takes (win_sel7).  With one buffer
+                // (more bitsliced waves than the LDS has room for: measurement
+                // settings of hy_t) those batches run full rounds.
+                const uint32_t q16 = 16u * (lane >> 3);
+                const uint32_t bbase = recw + 256u + q16, wnd = beta >> 2;
+                const bool cross = (beta & 3u) == 3u;
+                win = !hi && (dbl || !cross);
+                const bool first = (beta & 3u) == 0 && (beta == 0 || !dbl);
+                if (!hi && (first || (cross && dbl))) {
+                    // the octet's lanes each compute A and B byte-wise (S-box in
+                    // LDS) and write an eighth of the planes
+                    const uint32_t wn = first ? wnd : wnd + 1u;
+                    // (i = 0 on the lanes without a record: any nonce will do)
+                    const uint4 nvr = load_partial(b.nonce + 12 * i, 12);
+                    uint32_t A, Bw[4];
+                    bs8::win_words(rk, nvr.x, nvr.y, nvr.z, wn, SboxLds{sbox}, A, Bw);
+                    lds_st128(bbase + (dbl ? 1024u * (wn & 1u) : 0u) + 128u * l,
+                              make_uint4(bs8::rec_plane(Bw, l), bs8::rec_plane(Bw, 8 + l),
+                                         bs8::rec_plane(Bw, 16 + l), bs8::rec_plane(Bw, 24 + l)));
+                    lds_st32(recw + q16 + 128u * (l >> 2) + 4u * (l & 3u), bs8::a_plane(A, l));
+                    __builtin_amdgcn_wave_barrier();
+                }
+                if (win) {
+                    // column 0 after round 1: A ^ V[rho][beta % 4]
+                    const uint32_t va = vtab + 256u * (beta & 3u) + 16u * (rho & 7u);
+                    const uint4 a0 = lds_u128(recw + q16), a1 = lds_u128(recw + q16 + 128u);
+                    const uint4 v0 = lds_u128(va), v1 = lds_u128(va + 128u);
+                    uint32_t x[8] = {a0.x ^ v0.x, a0.y ^ v0.y, a0.z ^ v0.z, a0.w ^ v0.w,
+                                     a1.x ^ v1.x, a1.y ^ v1.y, a1.z ^ v1.z, a1.w ^ v1.w};
+                    // block 7 of the lanes rho >= 6 in a crossing batch: the next window's planes
+                    bs8::win_rounds(x, WinPlanes{bbase + (dbl ? 1024u * (wnd & 1u) : 0u),
+                                                 bbase + 1024u * ((wnd + 1u) & 1u),
+                                                 bs8::win_m7((c0 >> 3) & 1u ? 0xffffffffu : 0u), cross}, s);
+                } else {
+                    // full rounds (counters from 2^16 on: no TLS record gets
+                    // there): the first state rebuilt from the nonce
+                    const uint4 nvr = load_partial(b.nonce + 12 * i, 12);
+                    const uint32_t u[4] = {nvr.x ^ rk[0], nvr.y ^ rk[1], nvr.z ^ rk[2], rk[3]};
+                    bs8::first_state(u, c0, beta, hi, s);
+                }
+            } else {
+                // rows 0-1 come in after round 1's SubBytes (bs8::round1 sub01)
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const uint4 v = lds_u128((q < 4 && !hi ? rsub : recb) + 16u * q);
-                s[q >> 1][4 * (q & 1) + 0] = v.x;
-                s[q >> 1][4 * (q & 1) + 1] = v.y;
-                s[q >> 1][4 * (q & 1) + 2] = v.z;
-                s[q >> 1][4 * (q & 1) + 3] = v.w;
+                for (int q = 0; q < 8; ++q) {
+                    const uint4 v = lds_u128((q < 4 && !hi ? rsub : recb) + 16u * q);
+                    s[q >> 1][4 * (q & 1) + 0] = v.x;
+                    s[q >> 1][4 * (q & 1) + 1] = v.y;
+                    s[q >> 1][4 * (q & 1) + 2] = v.z;
+                    s[q >> 1][4 * (q & 1) + 3] = v.w;
+                }
+                uint32_t lanec[kS + 3], kmask;
+                bs8::lane_consts<kS>(c0, lanec, kmask);
+#pragma unroll
+                for (int bb = 0; bb < (int)kS + 3; ++bb) s[3 - (bb >> 3)][bb & 7] ^= lanec[bb];
+                bs8::ctr_planes<kS + 3, 16, kS + 3>(s, kmask, beta);
+                if (hi) bs8::ctr_planes<16, 32, kS + 3>(s, kmask, beta);
             }
-            uint32_t lanec[kS + 3], kmask;
-            bs8::lane_consts<kS>(c0, lanec, kmask);
-#pragma unroll
-            for (int bb = 0; bb < (int)kS + 3; ++bb) s[3 - (bb >> 3)][bb & 7] ^= lanec[bb];
-            bs8::ctr_planes<kS + 3, 16, kS + 3>(s, kmask, beta);
-            if (hi) bs8::ctr_planes<16, 32, kS + 3>(s, kmask, beta);
             // PRE: the batch's payload is loaded before the cipher runs, so
             // the XOR does not wait for HBM (32 VGPRs live across encrypt():
             // only at three waves per SIMD; at four the seal kernel spilled
@@ -522,8 +642,11 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
                     dp[q] = kNt ? gload16u_nt(in + 16u * (blk0 + LPR * q)) : gload16u(in + 16u * (blk0 + LPR * q));
             }
 
+            // one rolled loop for both: rounds 3 .. NR after the window path,
+            // 2 .. NR after round 1 in full
             uint32_t w[4][8];
-            bs8::encrypt<NR>(s, km, w, hi);
+            if (!win) bs8::round1(s, km, WIN || hi);
+            bs8::rounds_from<NR>(s, km, w, win ? 3 : 2);
             uint4 ks[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) ks[j] = make_uint4(w[0][j], w[1][j], w[2][j], w[3][j]);
@@ -552,7 +675,7 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
     // E_K(J0) precomputed per slot (slot 2 t; hy_mask_kernel, kt_mask_kernel),
     // loaded here so the lift below covers the load
     uint4 mask = make_uint4(0, 0, 0, 0);
-    if (mt && valid) mask = gload16(reinterpret_cast<const uint8_t*>(mt + 2 * t));
+    if (mt && valid) mask = gload16(reinterpret_cast<const uint8_t*>(mt + 2 * slot()));
     // lift by H^(LPR - l) and XOR-reduce over the record's lanes
     uint4 yn = norm4(y);
     if (yn.x | yn.y | yn.z | yn.w) yn = gf128_mul(yn, kc.hpow(LPR - l));
@@ -588,7 +711,11 @@ __device__ __forceinline__ void octet_job(const KC& kc, const tg_batch& b,
         // (rho from a fresh lane index: held until here, it was the open
         // kernel's last spill)
         const uint32_t rz = ((fresh_lane() & kM) + nc + 1u) & kM;
-        const uint4 z = make_uint4(0, 0, 0, 0);
+        // (the zero made here: as a constant it was hoisted out of the
+        // persistent loop and held, or spilled, across every job)
+        uint32_t z0 = 0;
+        asm volatile("" : "+v"(z0));
+        const uint4 z = make_uint4(z0, z0, z0, z0);
         for (uint32_t blk = rz; blk < nfull; blk += LPR) store16(out + 16u * blk, z, aligned);
         if (tail && (nfull & kM) == rz) store_partial(out + 16u * nfull, z, tail);
     }
@@ -631,8 +758,9 @@ __global__ __launch_bounds__(kBs8Threads, 4) void gcm_bs8_kernel(const GcmKeyDev
 // (waves 0 .. nt-1 T-table at raised priority, the rest bitsliced), each
 // taking octet jobs (8 records) from a global queue until the batch is done,
 // so the LDS and the VALU are busy at the same time.
-// LDS: H^8 tables [0, 64K), Te0/Te2 copies [64K, 128K), S-box, then 1 KiB of
-// record planes per wave.
+// LDS: H^8 tables [0, 64K), Te0/Te2 copies [64K, 128K), S-box, round keys,
+// GHASH offset rows, the key's V table, then the waves' window areas by role
+// (kHyWin: 256 B per T-table wave, 2 304 B per bitsliced wave).
 // 1024 threads = 16 waves = 4 per SIMD at <= 128 VGPRs; 768 = 3 per SIMD
 // at <= 168 VGPRs, which lets the bitsliced waves prefetch their payload
 // (option hy_threads).
@@ -640,9 +768,23 @@ constexpr int kHyThreads = 1024;
 constexpr uint32_t kHySbox = 2 * 65536;
 constexpr uint32_t kHyRk = kHySbox + 256;               // 15 round keys (16 B each)
 constexpr uint32_t kHyJt = kHyRk + 256;                 // gmul_rot lane-offset rows
-constexpr uint32_t kHyKeys = kHyJt + 256;               // (unused: round 2's key-plane area)
-constexpr uint32_t kHyRecBase = kHyKeys + 2048;
-constexpr size_t kHyLds = kHyRecBase + (kHyThreads / 64) * kRecArea;   // for either size
+constexpr uint32_t kHyV = kHyJt + 256;                  // the key's V table (stage_vtab, 1 KiB)
+// The bitsliced waves' window areas (octet_job WIN), laid out by role: wave
+// nt + k has area k; the T-table waves have none.  An area holds eight
+// records' A planes (256 B) and two buffers of their B planes (2 x 1 KiB); 13
+// of them fit.  With more bitsliced waves (hy_t below 3 at 1024 threads:
+// measurement settings) every wave gets one buffer.
+constexpr uint32_t kHyWin = kHyV + 1024;
+constexpr uint32_t kHyBsArea = 256 + 2 * 1024, kHyBsArea1 = 256 + 1024;
+constexpr uint32_t kHyTArea = 2 * 128;   // a T-table wave: two buffers of eight records' window constants
+constexpr size_t kHyLds = kHyWin + 13 * kHyBsArea;   // for either size
+static_assert(kHyLds <= 163840 && kHyWin + (kHyThreads / 64) * kHyBsArea1 <= kHyLds, "hybrid LDS");
+#if defined(TG_HY_NO_WIN)   // A/B builds: full rounds 1-2 on the bitsliced waves (kRecArea per wave)
+constexpr bool kHyWinPath = false;
+static_assert(kHyWin + (kHyThreads / 64) * kRecArea <= kHyLds, "hybrid LDS");
+#else
+constexpr bool kHyWinPath = true;
+#endif
 static_assert(kTeBase == 65536, "Te block follows the GHASH tables");
 
 // The batch descriptor is read from memory per job (bp): held in SGPRs
@@ -701,13 +843,21 @@ __global__ __launch_bounds__(THREADS) void gcm_hy_kernel(const GcmKeyDev* __rest
     stage_te(reinterpret_cast<uint32_t*>(g_lds_bs8) + kTeBase / 4);
     stage_sbox(kHySbox);
     if (threadIdx.x < 4 * (NR + 1)) reinterpret_cast<uint32_t*>(g_lds_bs8)[kHyRk / 4 + threadIdx.x] = key->rk[threadIdx.x];
+    if constexpr (kHyWinPath) stage_vtab(kHyV, key->rk[3] >> 24);
     __syncthreads();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 #if defined(TG_TAIL_PROBE)
     tail_probe_start();
 #endif
     const uint64_t njobs = (bp->n + 7) / 8;
-    const uint32_t recw = kHyRecBase + wave * kRecArea;
+    // the bitsliced waves' window areas (kHyWin): two B buffers each when they fit
+    // and the T-table waves' (kHyTArea each, first)
+    const bool dbl = nt * kHyTArea + (THREADS / 64 - nt) * kHyBsArea <= kHyLds - kHyWin;
+    // (wave-uniform: kept in an SGPR across the persistent loop)
+    const uint32_t recw = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(!kHyWinPath ? kHyWin + wave * kRecArea
+              : wave < nt ? kHyWin + wave * kHyTArea
+                          : kHyWin + nt * kHyTArea + (wave - nt) * (dbl ? kHyBsArea : kHyBsArea1)));
 #if defined(TG_ROLE_PROBE)
     const uint64_t rp_t0 = __builtin_amdgcn_s_memtime();
     uint64_t rp_grab = 0;
@@ -723,7 +873,7 @@ __global__ __launch_bounds__(THREADS) void gcm_hy_kernel(const GcmKeyDev* __rest
         for (;;) {
             RP_GRAB_START
             uint32_t job = 0;
-            if ((threadIdx.x & 63u) == 0) job = atomicAdd(queue, 1u);
+            if (fresh_lane() == 0) job = atomicAdd(queue, 1u);   // (threadIdx.x would be held across the loop)
             job = (uint32_t)__builtin_amdgcn_readfirstlane((int)job);
             RP_GRAB_END
             if (job >= njobs) break;
@@ -731,8 +881,9 @@ __global__ __launch_bounds__(THREADS) void gcm_hy_kernel(const GcmKeyDev* __rest
             const tg_batch b = *bp;
             const uint32_t tid = hy_tid(wave);
             const uint4 jw = lds_u128(kHyJt + ((tid & 15u) << 4));
-            octet_job<NR, OPEN, true>(SingleKeyRowCtx{key, jw, masks, tid}, b, order, 8ull * job, recw, rk,
-                                      kHySbox, bs8::KeyPlanesVmemFolded{{krows}}, tid);
+            octet_job<NR, OPEN, true, bs8::KeyPlanesVmemFolded, SingleKeyRowCtx, false, 8, RkLds, kHyWinPath>(
+                SingleKeyRowCtx{key, jw, masks, tid}, b, order, 8ull * job, recw, rk, kHySbox,
+                bs8::KeyPlanesVmemFolded{{krows}}, tid);
         }
     } else {
         // The key rows by scalar loads (SGPR operands: the T gates issue at
@@ -743,7 +894,7 @@ __global__ __launch_bounds__(THREADS) void gcm_hy_kernel(const GcmKeyDev* __rest
         for (;;) {
             RP_GRAB_START
             uint32_t job = 0;
-            if ((threadIdx.x & 63u) == 0) job = atomicAdd(queue, 1u);
+            if (fresh_lane() == 0) job = atomicAdd(queue, 1u);   // (threadIdx.x would be held across the loop)
             job = (uint32_t)__builtin_amdgcn_readfirstlane((int)job);
             RP_GRAB_END
             if (job >= njobs) break;
@@ -751,9 +902,9 @@ __global__ __launch_bounds__(THREADS) void gcm_hy_kernel(const GcmKeyDev* __rest
             const tg_batch b = *bp;
             const uint32_t tid = hy_tid(wave);
             const uint4 jw = lds_u128(kHyJt + ((tid & 15u) << 4));
-            octet_job<NR, OPEN, false, bs8::KeyPlanesVmemFolded, SingleKeyRowCtx, (THREADS < 1024)>(
-                SingleKeyRowCtx{key, jw, masks, tid}, b, order, 8ull * job, recw, none, kHySbox,
-                bs8::KeyPlanesVmemFolded{{krows}}, tid);
+            octet_job<NR, OPEN, false, bs8::KeyPlanesVmemFolded, SingleKeyRowCtx, (THREADS < 1024), 8, RkLds,
+                      kHyWinPath>(SingleKeyRowCtx{key, jw, masks, tid}, b, order, 8ull * job, recw, none, kHySbox,
+                                  bs8::KeyPlanesVmemFolded{{krows}}, tid, kHyV, dbl);
         }
     }
 #if defined(TG_TAIL_PROBE)
