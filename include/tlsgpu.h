@@ -146,6 +146,12 @@ int tg_open(tg_key* k, const uint8_t* nonce, size_t noncelen,
  *   status   open only: status[i] = 1 authentic / 0 rejected (pt zeroed)
  * len == NULL means every record is fixed_len bytes.  Offsets with 16-byte
  * alignment take the vector path; any alignment is accepted.
+ * Nothing outside a record's own output extent and status[0..n) is written:
+ * a seal extent is len[i] + T bytes (ct || tag), an open extent len[i] bytes
+ * (the plaintext, or len[i] zero bytes for a rejected or skipped record; the
+ * tag and the rest of a partial last block are never stored behind it), at
+ * any alignment of either side.  Inputs (in, nonce, aad and every offset,
+ * length and index array) are never written.
  * Records are independent; nothing is ordered between them.  AES-CCM records
  * must be shorter than 2^28 - 32 bytes (the 3-byte CCM counter; TLS records
  * are at most 2^14 + 256). */
@@ -197,7 +203,23 @@ int tg_make_nonces(int mode, const uint8_t* iv, size_t ivlen, uint64_t seq0,
  *         plaintext), its length to data_len[i], the (inner) content type to
  *         ctype[i], and a TG_REC_* code to status[i].
  * For the vector path place records so the payload after the header (and
- * TLS 1.2 AES explicit nonce) is 16-byte aligned.  The tag is T bytes. */
+ * TLS 1.2 AES explicit nonce) is 16-byte aligned.  The tag is T bytes.
+ * Nothing outside a record's own extents and entries [0, n) of the result
+ * arrays (seal: wire_len; open: data_len, ctype, status) is written:
+ *   seal: in wire, the wire_len[i] bytes of the record.  In data, TLS 1.3
+ *         writes bytes [data_len[i], data_len[i] + 1 + pad_len[i]) of the
+ *         fragment's extent (the content type, then zeros) -- the one write
+ *         to an input; a TLS 1.2 seal leaves data as it was.  The data
+ *         extent needs no room for the tag.
+ *   open: in data, the inner plaintext's bytes: wire_len[i] - 5 - [8] - T
+ *         (TLS 1.3: content, type, then the padding's zeros; TLS 1.2: the
+ *         content), and nothing behind them.  For TG_REC_BAD_MAC those
+ *         bytes are zero; for a record refused before decryption
+ *         (TG_REC_TRUNCATED, TG_REC_LENGTH, TG_REC_BAD_TYPE,
+ *         TG_REC_BAD_VERSION, TG_REC_OVERFLOW by the header's length) not a
+ *         byte of data is written.  wire is never written.
+ * The offset arrays, seal's data_len / ctype / pad_len and open's wire_len
+ * are never written. */
 #define TG_TLS12 0x0303
 #define TG_TLS13 0x0304
 #define TG_REC_OK 0
