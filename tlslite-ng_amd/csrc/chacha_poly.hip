@@ -278,16 +278,34 @@ __device__ __forceinline__ void tiled_blocks(WaveTile& t, uint32_t lane,
 // finished pair has been read out of the rows (after the row pass of the
 // iteration that completes it), so it has the next ChaCha block to land;
 // the wait for it is the first LDS read of the next iteration.
+//
+// rel (wave-relative addressing, wave-uniform): the batch has fixed strides
+// and the wave's 64 records are all valid, aligned and within 2^31 bytes of
+// the first one in both buffers (wave_span_fits, keymath.h; chacha_kernel
+// decides per wave).  Row r's record then sits at w.in + r * in_stride, so a
+// transfer instruction of row group 32 g + 8 q takes a wave-uniform 64-bit
+// base, advanced by the pair's 64 p0 on the scalar side, plus a 32-bit
+// per-lane offset that does not change over the loop -- no pointer rows in
+// LDS and no per-lane 64-bit adds.  Both forms of a turn sit in one loop
+// behind a scalar branch: as two loops the kernel spilled.
+struct WaveRel {
+    const uint8_t* in;    // the wave's first record
+    uint8_t* out;
+    uint32_t in_stride, out_stride;
+};
+
 template <bool OPEN>
-__device__ __forceinline__ void tiled_blocks_dma(WaveTile& t, uint32_t lane,
+__device__ __forceinline__ void tiled_blocks_dma(WaveTile& t, uint32_t lane, bool rel, const WaveRel& w,
                                                  const uint32_t (&k)[8], uint4 nv, uint32_t jmin,
                                                  Poly32& p, uint32_t (&ks)[16]) {
     const uint32_t grp = lane >> 5, cq = lane & 7u, rq = lane >> 3;
+    // swz(32 g + 8 q + rq, cq) = cs ^ 4 (q & 1) for either group and any q:
+    // (r >> 1) & 7 = (rq >> 1) ^ 4 (q & 1) and r & 1 = rq & 1
+    const uint32_t cs = swz(rq, cq);
     auto fetch_pair = [&](uint32_t g, uint32_t p0, const uint4 (&P)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const uint32_t r = 32 * g + 8 * q + rq;
-            const uint32_t c = swz(r, cq);          // the chunk that lands in slot cq
+            const uint32_t c = cs ^ (4u * (q & 1)); // the chunk that lands in slot cq of row 32 g + 8 q + rq
             const uint32_t off = p0 + (c >> 2) < jmin ? 64 * p0 + 16 * c : 16 * (c & 3u);
 #if defined(TG_CHACHA_ILV)   // measurement build: the group's lines interleaved (wrong bytes, same volume)
             const uint4 b0 = t.ptr[32 * g];
@@ -312,10 +330,7 @@ __device__ __forceinline__ void tiled_blocks_dma(WaveTile& t, uint32_t lane,
         uint4 P[4], S[4];
         ptrs(g, P);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t r = 32 * g + 8 * q + rq;
-            S[q] = t.row[r][swz(r, cq)];
-        }
+        for (int q = 0; q < 4; ++q) S[q] = t.row[32 * g + 8 * q + rq][cs ^ (4u * (q & 1))];
         const uint32_t blk = p0 + (cq >> 2);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -330,34 +345,80 @@ __device__ __forceinline__ void tiled_blocks_dma(WaveTile& t, uint32_t lane,
         }
         if (p0 + 2 < jmin) fetch_pair(g, p0 + 2, P);
     };
-    {
+    // rel: a lane's source offsets (even and odd q), its store offset and its
+    // slot in a row are fixed; the rest of every address is wave-uniform.
+    const uint32_t vin[2] = {rq * w.in_stride + 16u * cs, rq * w.in_stride + 16u * (cs ^ 4u)};
+    const uint32_t vout = rq * w.out_stride + 16u * cq;
+    auto fetch_rel = [&](uint32_t g, uint32_t p0) {
+        // the pair's second block lies past the tile (odd jmin): its chunks
+        // re-read the first block's, in bounds and never used
+        const bool two = p0 + 1 < jmin;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint8_t* src = w.in + (32 * g + 8 * q) * w.in_stride + 64 * p0;
+            const uint32_t c = cs ^ (4u * (q & 1));
+            const uint32_t v = two ? vin[q & 1] : rq * w.in_stride + 16u * (c & 3u);
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void*)(src + v),
+                (__attribute__((address_space(3))) void*)(&t.row[32 * g + 8 * q][0]),
+                16, 0, 0);
+        }
+    };
+    auto turn_rel = [&](uint32_t g, uint32_t p0) {
+        uint4 S[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) S[q] = t.row[32 * g + 8 * q + rq][cs ^ (4u * (q & 1))];
+        const bool st = p0 + 1 < jmin || cq < 4;   // chunks of the block past the tile stay home
+        // (through an empty asm: the compiler would otherwise fold the lane's
+        // offset into a 64-bit per-lane base outside the loop and add to that)
+        uint32_t vo = vout;
+        __asm__ volatile("" : "+v"(vo));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint8_t* dst = w.out + (32 * g + 8 * q) * w.out_stride + 64 * p0;
+            if (st) gstore16(dst + vo, S[q]);
+        }
+        if (p0 + 2 < jmin) fetch_rel(g, p0 + 2);
+    };
+    if (rel) {
+        fetch_rel(0, 0);
+        fetch_rel(1, 0);
+    } else {
         uint4 P[4];
         ptrs(0, P);
         fetch_pair(0, 0, P);
         ptrs(1, P);
         fetch_pair(1, 0, P);
     }
+    // the lane's row: chunk h + c (h = 0 or 4, c < 4) sits at byte
+    // rowx ^ 16 (h + c), since swz(lane, h + c) = swz(lane, 0) ^ h ^ c
+    uint8_t* const rows = reinterpret_cast<uint8_t*>(&t.row[0][0]);
+    const uint32_t rowx = 128u * lane + 16u * swz(lane, 0);
     for (uint32_t i = 0; i <= jmin; ++i) {
         const uint32_t b = i - grp;                 // this lane's block
         const bool act = i >= grp && b < jmin;
         uint4 m[4];
         if (act) {
-            const uint32_t h = 4 * (b & 1u);
+            const uint32_t rh = rowx ^ (64u * (b & 1u));
             uint4 d[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) d[c] = t.row[lane][swz(lane, h + c)];
+            for (int c = 0; c < 4; ++c) d[c] = *reinterpret_cast<const uint4*>(rows + (rh ^ (16u * c)));
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const uint4 ct = make_uint4(d[c].x ^ ks[4 * c], d[c].y ^ ks[4 * c + 1], d[c].z ^ ks[4 * c + 2],
                                             d[c].w ^ ks[4 * c + 3]);
-                t.row[lane][swz(lane, h + c)] = ct;
+                *reinterpret_cast<uint4*>(rows + (rh ^ (16u * c))) = ct;
                 m[c] = OPEN ? d[c] : ct;
             }
         }
         __builtin_amdgcn_wave_barrier();
         // group A finished block i, group B block i - 1 (wave-uniform)
-        if (i < jmin && ((i & 1u) || i + 1 == jmin)) turn(0, i & ~1u);
-        if (i >= 1 && (((i - 1) & 1u) || i == jmin)) turn(1, (i - 1) & ~1u);
+        if (i < jmin && ((i & 1u) || i + 1 == jmin)) {
+            if (rel) turn_rel(0, i & ~1u); else turn(0, i & ~1u);
+        }
+        if (i >= 1 && (((i - 1) & 1u) || i == jmin)) {
+            if (rel) turn_rel(1, (i - 1) & ~1u); else turn(1, (i - 1) & ~1u);
+        }
         __builtin_amdgcn_wave_barrier();
         if (act) {
             chacha_block(k, b + 2, nv.x, nv.y, nv.z, ks);
@@ -425,22 +486,45 @@ __global__ __launch_bounds__(kChachaThreads, MINW) void chacha_kernel(
     // of lanes without a record of their own (past the batch, or a skipped
     // key) load from the first valid lane's record, which has >= jmin blocks.
     const uint64_t vmask = __ballot(valid);
-    const uint32_t jmin = (vmask && __all(!valid || aligned)) ? wave_min(valid ? nfull : 0xffffffffu) : 0;
+    // (the same in every lane; through readfirstlane the tile loop's control is scalar)
+    const uint32_t jmin = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)((vmask && __all(!valid || aligned)) ? wave_min(valid ? nfull : 0xffffffffu) : 0));
     uint32_t j0 = 0;
     if (jmin > 0) {
-        WaveTile& t = tiles[threadIdx.x >> 6];
+        const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        WaveTile& t = tiles[wv];
+        // Wave-relative addressing (tiled_blocks_dma): fixed strides, a full
+        // wave of valid aligned records, the tile's bytes of the 64 records
+        // within 2^31 of the first record's in both buffers.  Single key
+        // only: with the key in VGPRs as well the key-table kernels spilled.
+        WaveRel w = {nullptr, nullptr, 0, 0};
+        bool rel = DMA && !MULTIKEY && !order && !b.in_off && !b.out_off && vmask == ~0ull &&
+                   wave_span_fits(b.in_stride, 64ull * jmin) && wave_span_fits(b.out_stride, 64ull * jmin);
+#if defined(TG_CHACHA_ILV) || defined(TG_CHACHA_NO_WAVE_REL)   // measurement builds: the pointer rows only
+        rel = false;
+#endif
+        // the same in every lane: the tile loop branches on it on the scalar side
+        rel = __builtin_amdgcn_readfirstlane((int)rel) != 0;
+        if (rel) {
+            const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + 64u * wv;
+            w.in = b.in + first * b.in_stride;
+            w.out = b.out + first * b.out_stride;
+            w.in_stride = (uint32_t)b.in_stride;
+            w.out_stride = (uint32_t)b.out_stride;
+        }
         const int src = __ffsll((unsigned long long)vmask) - 1;
         const uint32_t in_lo = (uint32_t)__shfl((int)(uint32_t)(uintptr_t)in, src, 64);
         const uint32_t in_hi = (uint32_t)__shfl((int)(uint32_t)((uintptr_t)in >> 32), src, 64);
         const uint8_t* tile_in = valid ? in : reinterpret_cast<const uint8_t*>(((uint64_t)in_hi << 32) | in_lo);
-        t.ptr[lane] = make_uint4((uint32_t)(uintptr_t)tile_in, (uint32_t)((uintptr_t)tile_in >> 32),
-                                 (uint32_t)(uintptr_t)tile_out, (uint32_t)((uintptr_t)tile_out >> 32));
+        if (!rel)
+            t.ptr[lane] = make_uint4((uint32_t)(uintptr_t)tile_in, (uint32_t)((uintptr_t)tile_in >> 32),
+                                     (uint32_t)(uintptr_t)tile_out, (uint32_t)((uintptr_t)tile_out >> 32));
         t.skey[lane] = make_uint4(p.p0, p.p1, p.p2, p.p3);
         __builtin_amdgcn_wave_barrier();
-        if (DMA)
-            tiled_blocks_dma<OPEN>(t, lane, k, nv, jmin, p, ks);
-        else
+        if (!DMA)
             tiled_blocks<OPEN>(t, lane, k, nv, jmin, p, ks);
+        else
+            tiled_blocks_dma<OPEN>(t, lane, rel, w, k, nv, jmin, p, ks);
         j0 = jmin;
         const uint4 sk = t.skey[lane];
         p.p0 = sk.x; p.p1 = sk.y; p.p2 = sk.z; p.p3 = sk.w;

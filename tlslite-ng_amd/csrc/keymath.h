@@ -14,6 +14,19 @@
 
 namespace tg {
 
+// The ChaCha20-Poly1305 tile loop addresses a wave's 64 records from the first
+// one with 32-bit offsets when they lie at a fixed stride and their span --
+// the 64 slots of ``stride`` bytes, or up to the end of the last record's
+// ``extent`` bytes if that is further -- is below 2^31 bytes (chacha_poly.hip
+// WaveRel; tests/test_chacha_round1_rule.py holds the edges).
+TG_KM_HD uint64_t wave_span(uint64_t stride, uint64_t extent) {
+    return 63u * stride + (extent > stride ? extent : stride);
+}
+TG_KM_HD bool wave_span_fits(uint64_t stride, uint64_t extent) {
+    // stride and extent bounded first: the product cannot wrap
+    return stride < (1ull << 31) && extent < (1ull << 31) && wave_span(stride, extent) < (1ull << 31);
+}
+
 // a * b in GF(2^128) mod x^128 + x^7 + x^2 + x + 1, normal order (coefficient
 // of x^i at bit i, word 0 first), bitwise (key setup only).
 TG_KM_HD void gf_mul_norm(const uint32_t a[4], const uint32_t b[4], uint32_t r[4]) {
