@@ -437,6 +437,10 @@ int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
  *         after the IV), TG_REC_OK.  Under etm the MAC is checked before the
  *         block-multiple test.  For any status but TG_REC_OK data_len[i] = 0
  *         and every byte written to the record's data extent is zero again.
+ *         wire_len[i] < 5 is not even a header: no byte at wire_off[i] is
+ *         read, status[i] = TG_REC_BAD_MAC, ctype[i] = 0, data_len[i] = 0
+ *         and nothing is written to the data buffer (data_off[i] may point
+ *         anywhere).
  *         MAC-then-encrypt costs the same hash blocks and AES blocks whatever
  *         the decrypted bytes are (it depends on wire_len[i] and the MAC).
  * Nothing outside a record's own data and wire extents is written.  Any

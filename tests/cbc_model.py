@@ -113,9 +113,28 @@ def wire_len(mac, etm, n):
     return 5 + 16 + ((n + 16) // 16 * 16 + d if etm else (n + d + 16) // 16 * 16)
 
 
+def mte_check(mac_key, mac, version, seq, ctype, plain):
+    """ct_check_cbc_mac_and_pad (constanttime.py:102-204) on the decrypted body
+    behind the IV block of a MAC-then-encrypt record: the fragment, or None
+    for TLSBadRecordMAC.  No cipher involved."""
+    plain = bytes(plain)
+    d, n = DIGEST[mac], len(plain)
+    if d + 1 > n:
+        return None
+    padlen = plain[-1]
+    pad_start = max(0, n - padlen - 1)
+    mac_start = max(0, pad_start - d)
+    bad = any(b != padlen for b in plain[max(pad_start, n - 256):])
+    want = record_mac(mac, mac_key, seq, ctype, version, plain[:mac_start])
+    bad |= not hmac.compare_digest(want, plain[mac_start:mac_start + d])
+    return None if bad else plain[:mac_start]
+
+
 def open_record(enc_key, mac_key, mac, version, etm, seq, wire, recv_limit=0):
     """(verdict, content type, plaintext) of one wire record."""
     wire = bytes(wire)
+    if len(wire) < 5:                         # not even a header (tg_cbc_records: type 0, nothing written)
+        return "TLSBadRecordMAC", 0, b""
     limit = recv_limit or 2 ** 14
     d = DIGEST[mac]
     ctype, hlen = wire[0], struct.unpack(">H", wire[3:5])[0]
@@ -141,18 +160,9 @@ def open_record(enc_key, mac_key, mac, version, etm, seq, wire, recv_limit=0):
         if len(body) % 16:
             return "TLSDecryptionFailed", ctype, b""
         plain = cbc_decrypt(enc_key, body[:16], body[16:]) if len(body) > 16 else b""
-        n = len(plain)
-        if d + 1 > n:
+        data = mte_check(mac_key, mac, version, seq, ctype, plain)
+        if data is None:
             return "TLSBadRecordMAC", ctype, b""
-        padlen = plain[-1]
-        pad_start = max(0, n - padlen - 1)
-        mac_start = max(0, pad_start - d)
-        bad = any(b != padlen for b in plain[max(pad_start, n - 256):])
-        want = record_mac(mac, mac_key, seq, ctype, version, plain[:mac_start])
-        bad |= not hmac.compare_digest(want, plain[mac_start:mac_start + d])
-        if bad:
-            return "TLSBadRecordMAC", ctype, b""
-        data = plain[:mac_start]
     if len(data) > limit:
         return "TLSRecordOverflow", ctype, b""
     return "ok", ctype, data

@@ -8,7 +8,10 @@
 //     (mac 1 / 2 / 3 = SHA-1 / -256 / -384; plain: the decrypted body behind
 //     its IV block, "-" when the record is not decrypted; status / len: what
 //     the reference's receiving RecordLayer gave).  The public checks, the
-//     verdict and the limit check must give exactly that.
+//     verdict and the limit check must give exactly that.  Every line is
+//     answered with "LINE k mac n compressions" (n: the decrypted length;
+//     the compression calls of its verdict, 0 when it was never decrypted),
+//     so that the caller can hold the count constant per (mac, n).
 // (b) For each MAC, valid records of one wire length with every padding
 //     length 0..255, and the same with a wrong padding byte and with a wrong
 //     MAC byte: the verdicts are right and the number of compression calls
@@ -56,8 +59,9 @@ static std::vector<uint8_t> unhex(const std::string& s) {
 template <class H>
 static uint32_t run_fixture(const std::vector<uint8_t>& key, uint32_t version, uint64_t seq, uint32_t type,
                             uint32_t limit, uint32_t hlen, uint32_t body, const std::vector<uint8_t>& plain,
-                            uint32_t* len) {
+                            uint32_t* len, unsigned long* cost) {
     *len = 0;
+    *cost = 0;
     uint32_t st = cbc::mte_public_status(H::kHash, hlen, body, limit);
     if (st != cbc::kRecOk) return st;
     if (plain.size() != body - 16) return 0xffffffffu;   // the test fed the wrong bytes
@@ -65,7 +69,9 @@ static uint32_t run_fixture(const std::vector<uint8_t>& key, uint32_t version, u
     cbc::hmac_midstates<H>(key.data(), (uint32_t)key.size(), &mid);
     // an exact-size copy, so that a read past the record shows under the sanitizer
     std::vector<uint8_t> p(plain);
+    const unsigned long before = tg_sha_count;
     const uint32_t bad = cbc::mte_verdict<H, HostMem>(mid, seq, type, version, p.data(), (uint32_t)p.size(), len);
+    *cost = tg_sha_count - before;
     st = cbc::final_status(bad, *len, limit);
     if (st != cbc::kRecOk) *len = 0;
     return st;
@@ -121,10 +127,12 @@ int main(int argc, char** argv) {
                   key_hex, plain_hex, &status, &len) == 11) {
         const std::vector<uint8_t> key = unhex(key_hex), plain = unhex(plain_hex);
         uint32_t got_len = 0, got;
-        if (mac == 1) got = run_fixture<Sha1>(key, version, seq, type, limit, hlen, body, plain, &got_len);
-        else if (mac == 2) got = run_fixture<Sha256>(key, version, seq, type, limit, hlen, body, plain, &got_len);
-        else got = run_fixture<Sha384>(key, version, seq, type, limit, hlen, body, plain, &got_len);
+        unsigned long cost = 0;
+        if (mac == 1) got = run_fixture<Sha1>(key, version, seq, type, limit, hlen, body, plain, &got_len, &cost);
+        else if (mac == 2) got = run_fixture<Sha256>(key, version, seq, type, limit, hlen, body, plain, &got_len, &cost);
+        else got = run_fixture<Sha384>(key, version, seq, type, limit, hlen, body, plain, &got_len, &cost);
         ++n;
+        printf("LINE %d %u %zu %lu\n", n, mac, plain.size(), cost);
         if (got != status || got_len != len) {
             printf("fixture %d (mac %u body %u): status %u len %u, want %u %u\n", n, mac, body, got, got_len, status,
                    len);

@@ -8,16 +8,25 @@ program (tests/native/cbc_verdict_check.cpp):
     the CPU model and handed over as a flat file);
 (b) valid records of one wire length with every padding length 0..255, and
     the same with a wrong padding byte or a wrong MAC, cost the same number of
-    compression calls, for each of the three hashes.
+    compression calls, for each of the three hashes;
+(c) the decrypted bodies of the MAC-then-encrypt padding grid (tests/
+    cbc_grid.py: every padding length at decrypted lengths from the smallest
+    a MAC fits in to 528, each with a mutated twin) follow the fixtures in the
+    same file, with the reference's verdicts of tests/golden/cbc_grid.json;
+    the compression calls of every line of one (MAC, decrypted length) are
+    the same, (13 + n - D - 1 + lenbytes) // block + 2.
 
 The program is built a second time with AddressSanitizer and UBSan and run
-directly: the fixtures include padding lengths that point outside the record."""
+directly: the fixtures include padding lengths that point outside the record,
+and every body sits in a heap buffer of exactly its size."""
+import collections
 import json
 import os
 import subprocess
 
 import pytest
 
+import cbc_grid
 import cbc_model
 from conftest import ROOT
 
@@ -44,9 +53,21 @@ def flat_file(tmp_path_factory):
                 MAC_CODE[c["mac"]], c["version"][0] << 8 | c["version"][1], o["seq"], wire[0],
                 o["recv_limit"] or 2 ** 14, hlen, len(body), c["mac_key"], plain, status, plen))
     assert len(lines) >= 80
+    nfix = len(lines)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "cbc_grid.json")))
+    for cfg, mode in cbc_grid.GRIDS:
+        if mode != "mte":
+            continue
+        mac_key = cbc_grid.keys(cfg)[1].hex()
+        for r, (verdict, length) in zip(cbc_grid.records(cfg, mode, cbc_grid.hmac_fn),
+                                        cbc_grid.expected(golden, cfg, mode)):
+            lines.append("%d %d %d %d %d %d %d %s %s %d %d" % (
+                MAC_CODE[cfg.mac], cfg.version, r.seq, r.ctype, 2 ** 14, r.case.n + 16, r.case.n + 16, mac_key,
+                r.body.hex(), cbc_model.STATUS_CODE[verdict], length))
+    assert len(lines) - nfix == 2 * (1772 + 1744 + 1680) + 2008
     path = tmp_path_factory.mktemp("cbc") / "mte_open.txt"
     path.write_text("\n".join(lines) + "\n")
-    return str(path), len(lines)
+    return str(path), len(lines), nfix
 
 
 def _build(tmp_path, name, extra):
@@ -58,19 +79,30 @@ def _build(tmp_path, name, extra):
     return exe
 
 
-def _check(out, nfix):
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.strip().endswith("OK"), out.stdout
-    assert "FIXTURES n=%d bad=0" % nfix in out.stdout
-    work = [ln for ln in out.stdout.splitlines() if ln.startswith("WORK ")]
-    assert len(work) == 3 and all(ln.endswith("bad=0") for ln in work), out.stdout
+def _check(out, nlines, nfix):
+    report = "\n".join(ln for ln in out.stdout.splitlines() if not ln.startswith("LINE "))
+    assert out.returncode == 0, report[-4000:] + out.stderr[-4000:]
+    assert report.strip().endswith("OK"), report[-4000:]
+    assert "FIXTURES n=%d bad=0" % nlines in report
+    work = [ln for ln in report.splitlines() if ln.startswith("WORK ")]
+    assert len(work) == 3 and all(ln.endswith("bad=0") for ln in work), report[-4000:]
+    # the grid's lines: one compression count per (MAC, decrypted length), the formula's
+    counts = collections.defaultdict(set)
+    per_line = [ln.split() for ln in out.stdout.splitlines() if ln.startswith("LINE ")]
+    assert [int(f[1]) for f in per_line] == list(range(1, nlines + 1))
+    for f in per_line[nfix:]:
+        counts[int(f[2]), int(f[3])].add(int(f[4]))
+    macs = {v: k for k, v in MAC_CODE.items()}
+    assert len(counts) == 3 * 9
+    for (mac, n), seen in sorted(counts.items()):
+        assert seen == {cbc_grid.mte_compressions(macs[mac], n)}, (macs[mac], n, seen)
 
 
 def test_host_verdict_matches_reference_and_costs_constant_work(tmp_path, flat_file):
-    path, nfix = flat_file
+    path, nlines, nfix = flat_file
     out = subprocess.run([_build(tmp_path, "cbc_verdict_check", []), path], capture_output=True, text=True,
                          timeout=120)
-    _check(out, nfix)
+    _check(out, nlines, nfix)
     # the compression counts: blocks up to the longest message the record could hold, plus the outer one
     assert "WORK sha1 n=384 compressions=8 " in out.stdout      # (13 + 363 + 8) // 64 + 1 + 1
     assert "WORK sha256 n=384 compressions=7 " in out.stdout    # (13 + 351 + 8) // 64 + 1 + 1
@@ -78,8 +110,8 @@ def test_host_verdict_matches_reference_and_costs_constant_work(tmp_path, flat_f
 
 
 def test_host_verdict_under_sanitizers(tmp_path, flat_file):
-    path, nfix = flat_file
+    path, nlines, nfix = flat_file
     exe = _build(tmp_path, "cbc_verdict_check_san",
                  ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     out = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
-    _check(out, nfix)
+    _check(out, nlines, nfix)
