@@ -219,7 +219,39 @@ int tg_make_nonces(int mode, const uint8_t* iv, size_t ivlen, uint64_t seq0,
  *         TG_REC_BAD_VERSION, TG_REC_OVERFLOW by the header's length) not a
  *         byte of data is written.  wire is never written.
  * The offset arrays, seal's data_len / ctype / pad_len and open's wire_len
- * are never written. */
+ * are never written.
+ * Open's checks, in order; the first that fails is the record's status
+ * (B = wire_len[i] - 5, E = 8 for TLS 1.2 AES-GCM / AES-CCM, else 0):
+ *   1. wire_len[i] < 5, B < E or B - E < T   TG_REC_TRUNCATED
+ *   2. B > recv_limit + 2048, or TLS 1.3 and
+ *      B > recv_limit + 256                  TG_REC_OVERFLOW (by the header)
+ *   3. TLS 1.3: outer type != 23             TG_REC_BAD_TYPE
+ *   4. TLS 1.3: version != 0x0303            TG_REC_BAD_VERSION
+ *   5. TLS 1.3: header length != B           TG_REC_LENGTH
+ *      (TLS 1.2: the header's version and length bytes are not looked at,
+ *      its type goes into the AAD)
+ *   6. the tag                               TG_REC_BAD_MAC
+ *   7. TLS 1.3: inner plaintext > limit + 1  TG_REC_OVERFLOW
+ *   8. TLS 1.3: inner plaintext all zero     TG_REC_NO_CONTENT_TYPE
+ *   9. content > recv_limit                  TG_REC_OVERFLOW
+ * This is the reference's order (RecordSocket.recv, _decryptAndUnseal,
+ * recvRecord) but for 1 and 2, which cannot coincide with a header a socket
+ * delivers.  So a cut body wins over a wrong header, a bad tag over a
+ * refusal after decryption (7-9), the header's overflow over a bad tag.
+ * For every status but TG_REC_OK data_len[i] = 0 and ctype[i] = 0.  A record
+ * refused after decryption (7-9) has passed the tag: its authentic inner
+ * plaintext stays in its data extent; it is not zeroed.
+ * wire_len[i] < 5 is not even a header: bytes [0, wire_len[i]) at wire_off[i]
+ * are the only ones read, status[i] = TG_REC_TRUNCATED, ctype[i] = 0,
+ * data_len[i] = 0 and nothing is written to data.
+ * Unprotected TLS 1.3 records are NOT handled here.  With an encrypting read
+ * state the reference passes two kinds of record through undecrypted and
+ * gives them no sequence number (recvRecord :920-933): outer type 20
+ * (ChangeCipherSpec, any body), and outer type 21 with a body under 3 bytes
+ * while seqnum == 0 (an alert before the first protected record).  Here they
+ * get TG_REC_BAD_TYPE, or TG_REC_TRUNCATED where the body is shorter than the
+ * tag, and in a batch they would take a sequence number: the caller takes
+ * them out before batching. */
 #define TG_TLS12 0x0303
 #define TG_TLS13 0x0304
 #define TG_REC_OK 0
@@ -276,9 +308,15 @@ int tg_open_records(tg_key* k, const tg_records* r, void* stream);
  *              after the call seq_next[s] has advanced by the session's
  *              record count (sessions without records are untouched).  The
  *              assignment follows batch order and is deterministic.  On open
- *              every record of a session consumes a number whatever its
- *              status, as getSeqNumBytes() at the top of _decryptAndUnseal
- *              (recordlayer.py:782).  The numbers come from a stable sort
+ *              every record with session[i] < nsessions consumes a number
+ *              whatever its status.  The reference does so for every record
+ *              that reaches _decryptAndUnseal (getSeqNumBytes() at its top,
+ *              recordlayer.py:782) and differs for two kinds that do not: a
+ *              record refused by the header's length (RecordSocket.recv
+ *              :219-222, TG_REC_OVERFLOW before decryption) and an
+ *              unprotected TLS 1.3 record (see tg_records) consume no number
+ *              there.  The first is fatal to its connection either way; the
+ *              second must not be in the batch.  The numbers come from a stable sort
  *              of the batch by session (one algorithm, and no kernel with a
  *              private segment, at every n).
  *   seq_out    optional, n entries: the number record i was given, in either
@@ -286,7 +324,11 @@ int tg_open_records(tg_key* k, const tg_records* r, void* stream);
  * A record with session[i] >= nsessions is skipped: nothing is read past
  * either table and no sequence number is consumed; seal writes nothing to
  * wire and sets wire_len[i] = 0; open sets status[i] = TG_REC_BAD_SESSION,
- * data_len[i] = 0 and ctype[i] = 0 and writes nothing to data.
+ * data_len[i] = 0 and ctype[i] = 0 and writes nothing to data.  That test
+ * comes before every other; for an in-range record the order of open's
+ * checks, the 0 / 0 rule for every refusal, the plaintext left by a refusal
+ * after decryption, the wire_len[i] < 5 rule and the exclusion of unprotected
+ * TLS 1.3 records are those of tg_records.
  * n is at most 2^32 - 2 in either mode; a larger n is TG_EINVAL before anything
  * is launched.  Two calls that share seq_next must be ordered on one stream. */
 #define TG_REC_BAD_SESSION 8    /* session[i] >= nsessions: record skipped */

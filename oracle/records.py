@@ -5,7 +5,9 @@ tlslite/recordlayer.py: _getNonce :522-534, _encryptThenSeal :536-565,
 sendRecord :606-617 (TLS 1.3 inner plaintext), _decryptAndUnseal :780-824,
 _tls13_de_pad :863-884, and the record-size limits of RecordSocket.recv
 :219-222 and recvRecord :974-981 (TLSRecordOverflow).  Pinned against tests/golden/records.json, which
-the reference RecordLayer itself produced (tests/golden/make_golden_records.py).
+the reference RecordLayer itself produced (tests/golden/make_golden_records.py), and on the
+receive side, class by class, against its verdicts in tests/golden/rec_grid.json
+(tests/rec_grid.py).  Unprotected TLS 1.3 records (recvRecord :920-933) are not modelled.
 Status codes are include/tlsgpu.h TG_REC_*.
 """
 from . import oracle

@@ -222,6 +222,10 @@ __device__ __forceinline__ void finish_one(const R& r, uint64_t i, const RecScra
             plen = ct_len;
         }
         if (st == TG_REC_OK && plen > limit) st = TG_REC_OVERFLOW;                  // :980-981
+        if (st != TG_REC_OK) {   // refused after decryption: length and type 0 like every refusal;
+            plen = 0;            // the authentic plaintext stays in data
+            type = 0;
+        }
     }
     r.data_len[i] = plen;
     r.ctype[i] = type;

@@ -343,6 +343,14 @@ class RecordReader(object):
     (RecordSocket.recv), then per record the exception _decryptAndUnseal or
     _tls13_de_pad would raise; records before the failing one are returned
     by ``records()`` first and the error is raised on the next call.
+
+    Unprotected TLS 1.3 records are not handled: the reference passes an
+    outer-type-20 record (ChangeCipherSpec), and an outer-type-21 record of
+    fewer than 3 bytes while ``seqnum == 0``, through undecrypted and gives
+    them no sequence number (recvRecord :920-933).  Here they raise
+    (TLSUnexpectedMessage, or TLSBadRecordMAC where the body is shorter than
+    the tag) and would take a sequence number: the caller takes them out of
+    the stream before ``feed``.
     """
 
     def __init__(self, key, version, fixed_iv, seq0=0, recv_record_limit=2 ** 14,
