@@ -520,6 +520,95 @@ typedef struct tg_cbc_records {
 int tg_cbc_seal_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
 int tg_cbc_open_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
 
+/* AES-CBC + HMAC records of MANY sessions in one batch: the pending records of
+ * many RecordLayers of one CBC suite (one direction each) through one call --
+ * tg_session_records carried over to tg_cbc_records.  Both chains of a CBC +
+ * HMAC record are serial inside the record, so a batch fills the machine only
+ * with tens of thousands of records; a server has them spread over many
+ * connections, a few each.
+ *
+ * KEY TABLES.  tg_cbc_key_create_table builds a handle of nkeys rows (cipher
+ * key j at enc_keys + j keylen, MAC key j at mac_keys + j mackeylen, HOST
+ * memory); keylen, mackeylen and mac hold for every row -- one table, one
+ * suite.  The argument errors are tg_cbc_key_create's, and nkeys == 0.
+ * tg_cbc_key_create is the table of one row; tg_cbc_key_info reports keylen,
+ * mac and nkeys (any out pointer may be NULL).  A table handle passed to
+ * tg_cbc_seal_records / tg_cbc_open_records uses row 0.  tg_cbc_key_destroy
+ * frees either kind: it waits for the device and scrubs every row.
+ *
+ * tg_cbc_key_replace: row j of the HOST arrays (n x keylen, n x mackeylen;
+ *   mackeylen may differ from creation's, within the MAC's limit) becomes
+ *   entry slot[j] (slot in HOST memory, NULL = 0..n-1) of the LIVE handle.
+ *   The rows are built on the host, as creation builds them, and copied into
+ *   the table ordered on `stream`: batches enqueued on `stream` before the
+ *   call use the old rows, batches after it the new ones; work on other
+ *   streams must be ordered against it by the caller.  A slot >= nkeys is
+ *   skipped; the slots of one call must be DISTINCT.  The call blocks the
+ *   host until its copies have left the staging memory (it waits for the
+ *   stream's earlier work with them, not for the device) and scrubs the
+ *   staging before it returns.  n == 0 is TG_OK; NULL key or arrays, n >
+ *   nkeys and a bad mackeylen are TG_EINVAL before any HIP call.  One replace
+ *   at a time per handle.  (Deriving the rows on the device belongs with a
+ *   TLS 1.2 PRF on the device; there is none.)
+ *
+ * tg_cbc_seal_session_records / tg_cbc_open_session_records.  All arrays are
+ * DEVICE pointers; record i belongs to session s = session[i] and uses table
+ * row s.
+ *   Per RECORD everything is tg_cbc_records': the wire layout of both
+ *   constructions, the minimal padding, the order of open's checks and the
+ *   status codes, the wire_len[i] < 5 rule, the zeroed data extent for every
+ *   status but TG_REC_OK, "nothing outside a record's own extents is
+ *   written", any alignment, and MAC-then-encrypt open costing the same
+ *   whatever the decrypted bytes are.  version and etm are one per batch.
+ *   Per SESSION everything is tg_session_records': exactly one of seq
+ *   (explicit: record i has number seq[i]) and seq_next (counter mode:
+ *   nsessions counters; record i gets seq_next[s] as it was before the call
+ *   plus the number of earlier records of s in the batch, and seq_next[s]
+ *   advances by the session's record count; sessions without records are
+ *   untouched; on open every in-range record consumes a number whatever its
+ *   status); seq_out is optional and receives the number of every in-range
+ *   record; nsessions must equal the handle's nkeys; n <= 2^32 - 2; two calls
+ *   that share seq_next must be ordered on one stream.
+ *   A record with session[i] >= nsessions is skipped, and that test comes
+ *   before every other: nothing of the table, of its iv row or of its data /
+ *   wire is read (its offsets may point anywhere) and no number is consumed;
+ *   seal writes nothing to wire and sets wire_len[i] = 0; open sets
+ *   status[i] = TG_REC_BAD_SESSION, data_len[i] = 0, ctype[i] = 0 and writes
+ *   nothing to data.
+ * Every argument error (those of tg_cbc_records; both or neither of seq /
+ * seq_next; n too large; NULL session; nsessions != nkeys) is TG_EINVAL before
+ * any HIP call; n == 0 is TG_OK with nothing launched. */
+int tg_cbc_key_create_table(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys,
+                            size_t mackeylen, int mac, size_t nkeys, tg_cbc_key** out);
+int tg_cbc_key_info(const tg_cbc_key* k, size_t* keylen, int* mac, size_t* nkeys);
+int tg_cbc_key_replace(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys,
+                       const uint8_t* mac_keys, size_t mackeylen, uint64_t n, void* stream);
+
+typedef struct tg_cbc_session_records {
+    uint64_t n;
+    uint32_t version;           /* TG_TLS11 or TG_TLS12, one per batch */
+    uint32_t etm;               /* one per batch */
+    uint32_t recv_limit;        /* open: recv_record_limit (0 = 2^14) */
+    uint32_t reserved;          /* ignored */
+    uint64_t nsessions;         /* must equal the handle's nkeys */
+    const uint32_t* session;
+    const uint64_t* seq;        /* exactly one of seq / seq_next */
+    uint64_t* seq_next;
+    uint64_t* seq_out;          /* optional */
+    uint8_t* data;
+    const uint64_t* data_off;
+    uint32_t* data_len;
+    uint8_t* ctype;
+    const uint8_t* iv;          /* seal: n x 16 bytes */
+    uint8_t* wire;
+    const uint64_t* wire_off;
+    uint32_t* wire_len;
+    uint8_t* status;            /* open */
+} tg_cbc_session_records;
+
+int tg_cbc_seal_session_records(tg_cbc_key* k, const tg_cbc_session_records* r, void* stream);
+int tg_cbc_open_session_records(tg_cbc_key* k, const tg_cbc_session_records* r, void* stream);
+
 /* Host ingest pipeline (tlsgpu/ingest.py) -- the
  * batched counterpart of RecordSocket (recordlayer.py:35-237).
  * tg_scan_records (HOST memory, no GPU): walk the 5-byte record headers

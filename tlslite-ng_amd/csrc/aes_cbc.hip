@@ -1,5 +1,8 @@
 // aes_cbc.hip -- batched TLS 1.1 / 1.2 AES-CBC + HMAC records for gfx950:
-// tg_cbc_key_create / _destroy, tg_cbc_seal_records, tg_cbc_open_records.
+// the key handles (tg_cbc_key_create / _create_table / _info / _replace /
+// _destroy) and one connection direction per call (tg_cbc_seal_records,
+// tg_cbc_open_records).  The record arithmetic is cbc_dev.h's, shared with the
+// session-per-record kernels of aes_cbc_table.hip.
 //
 // Restates the block-cipher paths of tlslite/recordlayer.py for TLS >= 1.1,
 // one record per lane:
@@ -41,175 +44,17 @@
 // threads per workgroup, two workgroups per CU (128 / 160 KiB of LDS).  The
 // round keys (seal: the schedule, open: the inverse schedule with
 // InvMixColumns applied to rounds 1 .. Nr - 1) are wave-uniform in SGPRs.
-#include "aes_round.h"
 #include "api.h"
-#include "cbc_record.h"
+#include "cbc_dev.h"
 #include "runtime.h"
 
+#include <stdio.h>
 #include <string.h>
 
 #include <new>
 
 namespace tg {
-
-// One CBC + HMAC key in device memory.
-struct CbcKeyDev {
-    uint32_t ek[60];       // round keys, LE words of the key-schedule bytes
-    uint32_t dk[60];       // equivalent inverse cipher: dk[r] = ek[Nr - r], InvMixColumns for 0 < r < Nr
-    cbc::Mid mid;          // HMAC midstates (32-bit hashes in the low halves)
-    uint32_t rounds;
-    uint32_t mac;
-    uint32_t pad[2];
-};
-
-}  // namespace tg
-
-struct tg_cbc_key {
-    int device;
-    int rounds;
-    int mac;
-    tg::CbcKeyDev* dev_key;
-};
-
-namespace tg {
 namespace {
-
-static_assert(cbc::kRecOk == TG_REC_OK && cbc::kRecBadMac == TG_REC_BAD_MAC && cbc::kRecOverflow == TG_REC_OVERFLOW &&
-                  cbc::kRecDecryptFailed == TG_REC_DECRYPT_FAILED,
-              "cbc_record.h status codes");
-
-constexpr int kCbcThreads = 512;
-constexpr uint32_t kSiBase = 65536;                 // inverse S-box copies behind the Td block
-constexpr size_t kSealLds = 65536;
-constexpr size_t kOpenLds = 65536 + 256 * 16 * 4;
-
-extern __shared__ __attribute__((aligned(16))) uint4 g_lds_cbc[];
-
-// ---- Td0 and the inverse S-box, generated at compile time ----------------
-struct TdTable {
-    uint32_t td0[256];
-    uint32_t si[256];
-};
-
-constexpr uint8_t gf_mul(uint8_t a, uint8_t b) {
-    uint8_t p = 0;
-    for (int k = 0; k < 8; ++k) {
-        if (b & 1) p = (uint8_t)(p ^ a);
-        a = xtime(a);
-        b = (uint8_t)(b >> 1);
-    }
-    return p;
-}
-
-constexpr TdTable make_td() {
-    const TeTable te = make_te();
-    TdTable t = {};
-    for (int v = 0; v < 256; ++v) t.si[(te.te0[v] >> 8) & 0xff] = (uint32_t)v;   // byte 1 of Te0[v] = S[v]
-    for (int v = 0; v < 256; ++v) {
-        const uint8_t s = (uint8_t)t.si[v];
-        // column contribution of a row-0 byte: rows (0e s, 09 s, 0d s, 0b s), LE word
-        t.td0[v] = (uint32_t)gf_mul(s, 0x0e) | ((uint32_t)gf_mul(s, 0x09) << 8) |
-                   ((uint32_t)gf_mul(s, 0x0d) << 16) | ((uint32_t)gf_mul(s, 0x0b) << 24);
-    }
-    return t;
-}
-
-__constant__ TdTable c_td = make_td();
-
-// InvMixColumns of one column (LE word of its bytes): the host's inverse schedule.
-constexpr uint32_t inv_mix_column(uint32_t w) {
-    const uint8_t a0 = (uint8_t)w, a1 = (uint8_t)(w >> 8), a2 = (uint8_t)(w >> 16), a3 = (uint8_t)(w >> 24);
-    const uint8_t b0 = (uint8_t)(gf_mul(a0, 0x0e) ^ gf_mul(a1, 0x0b) ^ gf_mul(a2, 0x0d) ^ gf_mul(a3, 0x09));
-    const uint8_t b1 = (uint8_t)(gf_mul(a0, 0x09) ^ gf_mul(a1, 0x0e) ^ gf_mul(a2, 0x0b) ^ gf_mul(a3, 0x0d));
-    const uint8_t b2 = (uint8_t)(gf_mul(a0, 0x0d) ^ gf_mul(a1, 0x09) ^ gf_mul(a2, 0x0e) ^ gf_mul(a3, 0x0b));
-    const uint8_t b3 = (uint8_t)(gf_mul(a0, 0x0b) ^ gf_mul(a1, 0x0d) ^ gf_mul(a2, 0x09) ^ gf_mul(a3, 0x0e));
-    return (uint32_t)b0 | ((uint32_t)b1 << 8) | ((uint32_t)b2 << 16) | ((uint32_t)b3 << 24);
-}
-
-// The Td0 / Td2 copy block in stage_te's layout, then row x = 16 copies of Si[x].
-__device__ __forceinline__ void stage_td(uint4* lds) {
-#pragma unroll 4
-    for (int e = threadIdx.x; e < 256 * 16; e += blockDim.x) {
-        const uint32_t v = c_td.td0[e >> 4];
-        const uint32_t w = (e & 8) ? rotl32(v, 16) : v;
-        lds[e] = make_uint4(w, w, w, w);
-    }
-    for (int e = threadIdx.x; e < 256 * 4; e += blockDim.x) {
-        const uint32_t v = c_td.si[e >> 2];
-        lds[kSiBase / 16 + e] = make_uint4(v, v, v, v);
-    }
-}
-
-template <int K>
-__device__ __forceinline__ uint32_t Si(uint32_t x, uint32_t si4) {
-    return lds_u32(kSiBase + (((x >> (8 * K)) & 0xffu) << 6) + si4);
-}
-
-// Last round of the inverse cipher: InvSubBytes of the InvShiftRows bytes.
-__device__ __forceinline__ uint32_t inv_last(uint32_t sa, uint32_t sb, uint32_t sc, uint32_t sd, uint32_t rk,
-                                             uint32_t si4) {
-    return (Si<0>(sa, si4) | (Si<1>(sb, si4) << 8) | (Si<2>(sc, si4) << 16) | (Si<3>(sd, si4) << 24)) ^ rk;
-}
-
-// D_K(in) by the equivalent inverse cipher (FIPS-197 5.3.5; the reference's
-// Rijndael.decrypt, rijndael.py:1040-1083): column c of a round reads row r
-// from column c - r.
-template <int NR, class RK>
-__device__ __forceinline__ uint4 aes_dec_block(uint32_t lane4, uint32_t si4, const RK& dk, uint4 in) {
-    const uint4 k0 = dk.get(0);
-    uint32_t s0 = in.x ^ k0.x, s1 = in.y ^ k0.y, s2 = in.z ^ k0.z, s3 = in.w ^ k0.w;
-#pragma unroll
-    for (int r = 1; r < NR; ++r) {
-        const uint4 k = dk.get(r);
-        const uint32_t t0 = col(s0, s3, s2, s1, k.x, lane4);
-        const uint32_t t1 = col(s1, s0, s3, s2, k.y, lane4);
-        const uint32_t t2 = col(s2, s1, s0, s3, k.z, lane4);
-        const uint32_t t3 = col(s3, s2, s1, s0, k.w, lane4);
-        s0 = t0; s1 = t1; s2 = t2; s3 = t3;
-    }
-    const uint4 k = dk.get(NR);
-    return make_uint4(inv_last(s0, s3, s2, s1, k.x, si4), inv_last(s1, s0, s3, s2, k.y, si4),
-                      inv_last(s2, s1, s0, s3, k.z, si4), inv_last(s3, s2, s1, s0, k.w, si4));
-}
-
-// ---- global memory as cbc_record.h reads it -------------------------------
-typedef uint32_t u32_a1 __attribute__((aligned(1)));
-
-struct GMem {
-    __device__ static __forceinline__ cbc::W4 ld16(const uint8_t* p) {
-        const uint4 v = gload16u(p);
-        return cbc::W4{v.x, v.y, v.z, v.w};
-    }
-    __device__ static __forceinline__ cbc::W4 ldn(const uint8_t* p, uint32_t n) {
-        const uint4 v = load_partial(p, n);
-        return cbc::W4{v.x, v.y, v.z, v.w};
-    }
-    __device__ static __forceinline__ uint32_t ld4(const uint8_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return *(const __attribute__((address_space(1))) u32_a1*)p;
-#else
-        return 0;
-#endif
-    }
-    __device__ static __forceinline__ uint32_t ld1(const uint8_t* p) { return ((gptr_c)p)[0]; }
-};
-
-__device__ __forceinline__ void st4(uint8_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    *(__attribute__((address_space(1))) u32_a1*)p = v;
-#endif
-}
-
-template <class H>
-__device__ __forceinline__ void store_mac(uint8_t* p, const uint32_t dig[12]) {
-#pragma unroll
-    for (int k = 0; k < H::kHash / 4; ++k) st4(p + 4 * k, bswap32(dig[k]));
-}
-
-__device__ __forceinline__ void zero_bytes(uint8_t* p, uint32_t n, bool aligned) {   // n: multiple of 16
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (uint32_t k = 0; k < n; k += 16) store16(p + k, z, aligned);
-}
 
 // ---- seal ------------------------------------------------------------------
 template <int NR, class H, bool ETM>
@@ -426,48 +271,69 @@ int cbc_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream, bool open)
                            : launch0<14>(k->mac, k->dev_key, *r, open, s);
 }
 
-}  // namespace
-}  // namespace tg
+// ---- key handles: one row, or a table of them -------------------------------
+constexpr size_t kStageRows = 1024;   // tg_cbc_key_replace's pinned staging (624 KiB)
 
-using tg::fail;
-
-extern "C" {
-
-int tg_cbc_key_create(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_key, size_t mackeylen, int mac,
-                      tg_cbc_key** out) {
-    if (!out || !enc_key || !mac_key) return fail(TG_EINVAL, "null argument");
-    if (keylen != 16 && keylen != 32) return fail(TG_EINVAL, "enc key length must be 16 or 32, got %zu", keylen);
-    const int block = tg::mac_block(mac);
-    if (!block) return fail(TG_EINVAL, "unknown mac %d", mac);
-    if (mackeylen == 0 || mackeylen > (size_t)block)
-        return fail(TG_EINVAL, "mac key length must be 1..%d, got %zu", block, mackeylen);
-
-    tg::CbcKeyDev* img = new (std::nothrow) tg::CbcKeyDev();
-    tg_cbc_key* k = new (std::nothrow) tg_cbc_key();
-    if (!img || !k) {
-        delete img;
-        delete k;
-        return fail(TG_ENOMEM, "out of host memory");
+const char* key_error(size_t keylen, size_t mackeylen, int mac, char (&buf)[80]) {
+    if (keylen != 16 && keylen != 32) {
+        snprintf(buf, sizeof(buf), "enc key length must be 16 or 32, got %zu", keylen);
+        return buf;
     }
-    const int nr = tg::host::aes_round_words(enc_key, keylen, img->ek, nullptr);
+    const int block = mac_block(mac);
+    if (!block) {
+        snprintf(buf, sizeof(buf), "unknown mac %d", mac);
+        return buf;
+    }
+    if (mackeylen == 0 || mackeylen > (size_t)block) {
+        snprintf(buf, sizeof(buf), "mac key length must be 1..%d, got %zu", block, mackeylen);
+        return buf;
+    }
+    return nullptr;
+}
+
+// The device row of one (cipher key, MAC key) pair, built on the host.
+void build_row(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_key, size_t mackeylen, int mac,
+               CbcKeyDev* img) {
+    const int nr = host::aes_round_words(enc_key, keylen, img->ek, nullptr);
     for (int r = 0; r <= nr; ++r)
         for (int c = 0; c < 4; ++c) {
             const uint32_t w = img->ek[4 * (nr - r) + c];
-            img->dk[4 * r + c] = (r == 0 || r == nr) ? w : tg::inv_mix_column(w);
+            img->dk[4 * r + c] = (r == 0 || r == nr) ? w : inv_mix_column(w);
         }
-    if (mac == TG_MAC_SHA1) tg::cbc::hmac_midstates<tg::Sha1>(mac_key, (uint32_t)mackeylen, &img->mid);
-    else if (mac == TG_MAC_SHA256) tg::cbc::hmac_midstates<tg::Sha256>(mac_key, (uint32_t)mackeylen, &img->mid);
-    else tg::cbc::hmac_midstates<tg::Sha384>(mac_key, (uint32_t)mackeylen, &img->mid);
+    if (mac == TG_MAC_SHA1) cbc::hmac_midstates<Sha1>(mac_key, (uint32_t)mackeylen, &img->mid);
+    else if (mac == TG_MAC_SHA256) cbc::hmac_midstates<Sha256>(mac_key, (uint32_t)mackeylen, &img->mid);
+    else cbc::hmac_midstates<Sha384>(mac_key, (uint32_t)mackeylen, &img->mid);
     img->rounds = (uint32_t)nr;
     img->mac = (uint32_t)mac;
-    k->rounds = nr;
+}
+
+int key_create(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, size_t mackeylen, int mac,
+               size_t nkeys, tg_cbc_key** out) {
+    if (!out || !enc_keys || !mac_keys) return fail(TG_EINVAL, "null argument");
+    char buf[80];
+    if (const char* msg = key_error(keylen, mackeylen, mac, buf)) return fail(TG_EINVAL, "%s", msg);
+    if (nkeys == 0 || nkeys > 0xffffffffull) return fail(TG_EINVAL, "nkeys must be 1 .. 2^32 - 1, got %zu", nkeys);
+
+    CbcKeyDev* img = new (std::nothrow) CbcKeyDev[nkeys]();
+    tg_cbc_key* k = new (std::nothrow) tg_cbc_key();
+    if (!img || !k) {
+        delete[] img;
+        delete k;
+        return fail(TG_ENOMEM, "out of host memory");
+    }
+    for (size_t j = 0; j < nkeys; ++j)
+        build_row(enc_keys + j * keylen, keylen, mac_keys + j * mackeylen, mackeylen, mac, img + j);
+    k->rounds = keylen == 16 ? 10 : 14;
     k->mac = mac;
+    k->nkeys = nkeys;
     k->dev_key = nullptr;
+    k->stage = nullptr;
+    k->stage_done = nullptr;
     hipError_t e = hipGetDevice(&k->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&k->dev_key, sizeof(tg::CbcKeyDev));
-    if (e == hipSuccess) e = hipMemcpy(k->dev_key, img, sizeof(tg::CbcKeyDev), hipMemcpyHostToDevice);
-    tg::scrub(img, sizeof(*img));
-    delete img;
+    if (e == hipSuccess) e = hipMalloc((void**)&k->dev_key, nkeys * sizeof(CbcKeyDev));
+    if (e == hipSuccess) e = hipMemcpy(k->dev_key, img, nkeys * sizeof(CbcKeyDev), hipMemcpyHostToDevice);
+    scrub(img, nkeys * sizeof(CbcKeyDev));
+    delete[] img;
     if (e != hipSuccess) {
         if (k->dev_key) (void)hipFree(k->dev_key);
         delete k;
@@ -477,16 +343,100 @@ int tg_cbc_key_create(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_
     return TG_OK;
 }
 
+// tg_cbc_key_replace.  The rows are built in pinned staging, kStageRows at a
+// time; each run of consecutive slots is one copy on the stream; the host
+// waits on an event behind a chunk's copies (not on the device) and scrubs
+// the staging before it is filled again or the call returns.
+int key_replace(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
+                size_t mackeylen, uint64_t n, hipStream_t s) {
+    const size_t keylen = k->rounds == 10 ? 16 : 32;
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != k->device) HIP_TRY(hipSetDevice(k->device));
+    if (!k->stage) {
+        HIP_TRY(hipHostMalloc((void**)&k->stage, kStageRows * sizeof(CbcKeyDev), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&k->stage_done, hipEventDisableTiming));
+    }
+    for (uint64_t base = 0; base < n; base += kStageRows) {
+        const size_t m = (size_t)(n - base < kStageRows ? n - base : kStageRows);
+        hipError_t e = hipSuccess;
+        for (size_t j = 0; j < m && e == hipSuccess;) {
+            const uint64_t first = slot ? slot[base + j] : base + j;
+            if (first >= k->nkeys) {   // skipped: nothing of the table is touched
+                ++j;
+                continue;
+            }
+            size_t run = 0;
+            while (j + run < m && (slot ? slot[base + j + run] : base + j + run) == first + run &&
+                   first + run < k->nkeys) {
+                const uint64_t row = base + j + run;
+                build_row(enc_keys + row * keylen, keylen, mac_keys + row * mackeylen, mackeylen, k->mac,
+                          k->stage + j + run);
+                ++run;
+            }
+            e = hipMemcpyAsync(k->dev_key + first, k->stage + j, run * sizeof(CbcKeyDev), hipMemcpyHostToDevice,
+                               s);
+            j += run;
+        }
+        if (e == hipSuccess) e = hipEventRecord(k->stage_done, s);
+        if (e == hipSuccess) e = hipEventSynchronize(k->stage_done);
+        else (void)hipStreamSynchronize(s);   // copies already queued must be done with the staging
+        scrub(k->stage, m * sizeof(CbcKeyDev));
+        if (e != hipSuccess) return fail(TG_EHIP, "cbc key replace: %s", hipGetErrorString(e));
+    }
+    return TG_OK;
+}
+
+}  // namespace
+}  // namespace tg
+
+using tg::fail;
+
+extern "C" {
+
+int tg_cbc_key_create(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_key, size_t mackeylen, int mac,
+                      tg_cbc_key** out) {
+    return tg::key_create(enc_key, keylen, mac_key, mackeylen, mac, 1, out);
+}
+
+int tg_cbc_key_create_table(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, size_t mackeylen,
+                            int mac, size_t nkeys, tg_cbc_key** out) {
+    return tg::key_create(enc_keys, keylen, mac_keys, mackeylen, mac, nkeys, out);
+}
+
+int tg_cbc_key_info(const tg_cbc_key* k, size_t* keylen, int* mac, size_t* nkeys) {
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (keylen) *keylen = k->rounds == 10 ? 16 : 32;
+    if (mac) *mac = k->mac;
+    if (nkeys) *nkeys = k->nkeys;
+    return TG_OK;
+}
+
+int tg_cbc_key_replace(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
+                       size_t mackeylen, uint64_t n, void* stream) {
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (n > k->nkeys)
+        return fail(TG_EINVAL, "%llu rows for a table of %zu keys", (unsigned long long)n, k->nkeys);
+    if (n == 0) return TG_OK;
+    if (!enc_keys || !mac_keys) return fail(TG_EINVAL, "null argument");
+    char buf[80];
+    if (const char* msg = tg::key_error(k->rounds == 10 ? 16 : 32, mackeylen, k->mac, buf))
+        return fail(TG_EINVAL, "%s", msg);
+    return tg::key_replace(k, slot, enc_keys, mac_keys, mackeylen, n, static_cast<hipStream_t>(stream));
+}
+
 int tg_cbc_key_destroy(tg_cbc_key* k) {
     if (!k) return TG_OK;
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess && cur != k->device) (void)hipSetDevice(k->device);
-    // batches may still be reading the key on callers' streams
+    // batches may still be reading the rows on callers' streams
     (void)hipDeviceSynchronize();
     if (k->dev_key) {
-        (void)hipMemset(k->dev_key, 0, sizeof(tg::CbcKeyDev));
+        (void)hipMemset(k->dev_key, 0, k->nkeys * sizeof(tg::CbcKeyDev));
         (void)hipFree(k->dev_key);
     }
+    if (k->stage) (void)hipHostFree(k->stage);   // scrubbed at the end of every replace
+    if (k->stage_done) (void)hipEventDestroy(k->stage_done);
     delete k;
     return TG_OK;
 }

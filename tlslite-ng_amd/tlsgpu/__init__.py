@@ -15,7 +15,7 @@ from .records import (TLS11, TLS12, TLS13, open_records, open_session_records, s
                       seal_session_records)
 from . import keysetup  # noqa: F401
 from . import cbc  # noqa: F401
-from .cbc import CbcKey  # noqa: F401
+from .cbc import CbcKey, CbcSessions  # noqa: F401
 from .sessions import Sessions  # noqa: F401
 from .ingest import RecordReader, RecordWriter  # noqa: F401
 

@@ -35,7 +35,8 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_scratch_info", "tg_scratch_trim", "tg_helper_info", "tg_host_copy", "tg_host_copy_rows",
            "tg_seal_session_records", "tg_open_session_records", "tg_key_replace_device",
            "tg_sessions_rekey", "tg_cbc_key_create", "tg_cbc_key_destroy", "tg_cbc_seal_records",
-           "tg_cbc_open_records")
+           "tg_cbc_open_records", "tg_cbc_key_create_table", "tg_cbc_key_info", "tg_cbc_key_replace",
+           "tg_cbc_seal_session_records", "tg_cbc_open_session_records")
 
 TG_REKEY_INSTALL = 0
 TG_REKEY_UPDATE = 1
@@ -159,6 +160,31 @@ class TgCbcRecords(ctypes.Structure):
     ]
 
 
+class TgCbcSessionRecords(ctypes.Structure):
+    """``struct tg_cbc_session_records`` (include/tlsgpu.h)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("version", ctypes.c_uint32),
+        ("etm", ctypes.c_uint32),
+        ("recv_limit", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("nsessions", ctypes.c_uint64),
+        ("session", ctypes.c_void_p),
+        ("seq", ctypes.c_void_p),
+        ("seq_next", ctypes.c_void_p),
+        ("seq_out", ctypes.c_void_p),
+        ("data", ctypes.c_void_p),
+        ("data_off", ctypes.c_void_p),
+        ("data_len", ctypes.c_void_p),
+        ("ctype", ctypes.c_void_p),
+        ("iv", ctypes.c_void_p),
+        ("wire", ctypes.c_void_p),
+        ("wire_off", ctypes.c_void_p),
+        ("wire_len", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 class TlsGpuError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libtlsgpu error %d: %s" % (code, msg))
@@ -231,6 +257,13 @@ def load():
         l.tg_cbc_key_destroy.argtypes = [p]
         l.tg_cbc_seal_records.argtypes = [p, ctypes.POINTER(TgCbcRecords), p]
         l.tg_cbc_open_records.argtypes = [p, ctypes.POINTER(TgCbcRecords), p]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_cbc_key_create_table"):
+        l.tg_cbc_key_create_table.argtypes = [p, sz, p, sz, i, sz, ctypes.POINTER(ctypes.c_void_p)]
+        l.tg_cbc_key_info.argtypes = [p, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(sz)]
+        l.tg_cbc_key_replace.argtypes = [p, p, p, p, sz, u64, p]
+        l.tg_cbc_seal_session_records.argtypes = [p, ctypes.POINTER(TgCbcSessionRecords), p]
+        l.tg_cbc_open_session_records.argtypes = [p, ctypes.POINTER(TgCbcSessionRecords), p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):

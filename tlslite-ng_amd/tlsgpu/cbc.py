@@ -17,6 +17,12 @@ or encrypt-then-MAC (``_encryptThenMAC`` :500-520, ``_macThenDecrypt``
   ``wire_len[i] - 21`` bytes per record; a rejected record's extent is zero
   afterwards.
 
+The pending records of MANY connections of one suite go through one call
+with a key table (``CbcKey.table``), a session index per record and explicit
+numbers or per-session counters (``seal_session_records`` /
+``open_session_records``, ``CbcSessions``; tg_cbc_seal_session_records /
+tg_cbc_open_session_records).
+
 All buffers are device tensors (or raw device pointers).
 """
 import ctypes
@@ -45,6 +51,59 @@ class CbcKey(object):
                                                MACS[mac], ctypes.byref(h)))
         self.handle = h
 
+    @classmethod
+    def table(cls, enc_keys, mac_keys, mac):
+        """One direction of many connections of one suite
+        (tg_cbc_key_create_table): ``enc_keys`` and ``mac_keys`` are sequences
+        of byte strings, one pair per session, all cipher keys of one length
+        and all MAC keys of one length.  Entry ``s`` serves the records whose
+        session index is ``s`` (``CbcSessions``, ``seal_session_records``)."""
+        if mac not in MACS:
+            raise ValueError("mac must be one of %s" % ", ".join(sorted(MACS)))
+        enc, keylen, mk, mackeylen, n = _key_rows(enc_keys, mac_keys)
+        if n == 0:
+            raise ValueError("a key table needs at least one key")
+        self = cls.__new__(cls)
+        self.mac = mac
+        self.macLength = MAC_LENGTH[mac]
+        self._lib = _lib.load()
+        self.handle = None
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.tg_cbc_key_create_table(enc, keylen, mk, mackeylen, MACS[mac], n,
+                                                     ctypes.byref(h)))
+        self.handle = h
+        return self
+
+    @property
+    def nkeys(self):
+        """Entries of the handle (1 for a key made by the constructor)."""
+        n = ctypes.c_size_t(0)
+        _lib.check(self._lib.tg_cbc_key_info(_key(self).handle, None, None, ctypes.byref(n)))
+        return n.value
+
+    def replace(self, slots, enc_keys, mac_keys, stream=None):
+        """New keys for the entries ``slots`` (host integers, distinct; ``None``
+        = the first ``len(enc_keys)``) of the live table (tg_cbc_key_replace):
+        pair j becomes entry ``slots[j]``; a slot that is not below ``nkeys``
+        is skipped.  Ordered on ``stream``: batches enqueued there before the
+        call use the old keys, batches after it the new ones."""
+        enc, keylen, mk, mackeylen, n = _key_rows(enc_keys, mac_keys)
+        arr = None
+        if slots is not None:
+            slots = [int(x) for x in slots]
+            if len(slots) != n:
+                raise ValueError("one slot per key pair")
+            arr = (ctypes.c_uint32 * n)(*slots)
+        if n and keylen != self._keylen():
+            raise ValueError("cipher keys must have the table's length (%d)" % self._keylen())
+        _lib.check(self._lib.tg_cbc_key_replace(_key(self).handle, arr, enc, mk, mackeylen, n,
+                                                _stream(stream)))
+
+    def _keylen(self):
+        n = ctypes.c_size_t(0)
+        _lib.check(self._lib.tg_cbc_key_info(_key(self).handle, ctypes.byref(n), None, None))
+        return n.value
+
     def close(self):
         if self.handle is not None:
             self._lib.tg_cbc_key_destroy(self.handle)
@@ -55,6 +114,17 @@ class CbcKey(object):
             self.close()
         except Exception:   # noqa: BLE001 -- interpreter shutdown
             pass
+
+
+def _key_rows(enc_keys, mac_keys):
+    """``(cipher keys packed, keylen, MAC keys packed, mackeylen, n)``."""
+    enc = [bytes(k) for k in enc_keys]
+    mk = [bytes(k) for k in mac_keys]
+    if len(enc) != len(mk):
+        raise ValueError("one MAC key per cipher key")
+    if len(set(map(len, enc))) > 1 or len(set(map(len, mk))) > 1:
+        raise ValueError("the keys of a table have one length (one suite per table)")
+    return (b"".join(enc), len(enc[0]) if enc else 0, b"".join(mk), len(mk[0]) if mk else 0, len(enc))
 
 
 def _records(n, version, etm, seq0, data, data_off, data_len, ctype, wire, wire_off, wire_len,
@@ -102,3 +172,112 @@ def open_records(key, version, etm, seq0, n, data, data_off, data_len, ctype, st
     r = _records(n, version, etm, seq0, data, data_off, data_len, ctype, wire, wire_off, wire_len,
                  status=status, recv_limit=recv_limit)
     _lib.check(k._lib.tg_cbc_open_records(k.handle, ctypes.byref(r), _stream(stream)))
+
+
+def _session_records(key, n, version, etm, session, seq, seq_next, seq_out, data, data_off, data_len,
+                     ctype, wire, wire_off, wire_len, iv=None, status=None, recv_limit=0):
+    r = _lib.TgCbcSessionRecords()
+    r.n = int(n)
+    r.version = int(version)
+    r.etm = int(etm)
+    r.recv_limit = int(recv_limit)
+    r.nsessions = key.nkeys
+    r.session = _ptr(session, "session")
+    r.seq = _ptr(seq, "seq")
+    r.seq_next = _ptr(seq_next, "seq_next")
+    r.seq_out = _ptr(seq_out, "seq_out")
+    r.data = _ptr(data, "data")
+    r.data_off = _ptr(data_off, "data_off")
+    r.data_len = _ptr(data_len, "data_len")
+    r.ctype = _ptr(ctype, "ctype")
+    r.iv = _ptr(iv, "iv")
+    r.wire = _ptr(wire, "wire")
+    r.wire_off = _ptr(wire_off, "wire_off")
+    r.wire_len = _ptr(wire_len, "wire_len")
+    r.status = _ptr(status, "status")
+    return r
+
+
+def seal_session_records(key, version, etm, session, n, data, data_off, data_len, ctype, iv, wire,
+                         wire_off, wire_len, seq=None, seq_next=None, seq_out=None, stream=None):
+    """``seal_records`` for the records of many sessions
+    (tg_cbc_seal_session_records): record i uses entry ``session[i]`` of the
+    table ``key`` and the number ``seq[i]``, or -- with ``seq_next``, one
+    device int64 counter per entry -- the session's counter plus the record's
+    rank among the session's records of the batch; the counters advance.  A
+    record whose session is out of range is skipped (``wire_len[i] = 0``)."""
+    k = _key(key)
+    r = _session_records(k, n, version, etm, session, seq, seq_next, seq_out, data, data_off, data_len,
+                         ctype, wire, wire_off, wire_len, iv=iv)
+    _lib.check(k._lib.tg_cbc_seal_session_records(k.handle, ctypes.byref(r), _stream(stream)))
+
+
+def open_session_records(key, version, etm, session, n, wire, wire_off, wire_len, data, data_off,
+                         data_len, ctype, status, seq=None, seq_next=None, seq_out=None, stream=None,
+                         recv_limit=0):
+    """``open_records`` for the records of many sessions
+    (tg_cbc_open_session_records); every in-range record consumes a number
+    whatever its status, a record whose session is out of range gets status 8
+    (bad_session) and consumes none."""
+    k = _key(key)
+    r = _session_records(k, n, version, etm, session, seq, seq_next, seq_out, data, data_off, data_len,
+                         ctype, wire, wire_off, wire_len, status=status, recv_limit=recv_limit)
+    _lib.check(k._lib.tg_cbc_open_session_records(k.handle, ctypes.byref(r), _stream(stream)))
+
+
+class CbcSessions(object):
+    """Many sessions' CBC record-layer state for one direction: the key table
+    and one sequence counter per session on the device -- ``Sessions`` for the
+    block-cipher suites.  ``seal`` / ``open`` take a batch that interleaves the
+    pending records of any of the sessions; without ``seq`` each session's
+    records are numbered in batch order from its counter, which advances
+    (``getSeqNumBytes`` per record)."""
+
+    def __init__(self, table, version, etm, seq_next=None):
+        import torch
+        if not isinstance(table, CbcKey) or table.handle is None:
+            raise TypeError("table must be an open tlsgpu.CbcKey")
+        n = table.nkeys
+        if seq_next is None:
+            seq_next = torch.zeros(n, dtype=torch.int64, device="cuda")
+        elif seq_next.numel() != n or seq_next.dtype != torch.int64:
+            raise ValueError("seq_next must hold one int64 counter per key of the table")
+        self.table, self.version, self.etm, self.seq_next = table, int(version), int(etm), seq_next
+
+    def __len__(self):
+        return self.seq_next.numel()
+
+    def seq(self):
+        """The per-session sequence counters (device int64 tensor)."""
+        return self.seq_next
+
+    def replace(self, slots, enc_keys, mac_keys, stream=None):
+        """New connections take the sessions ``slots`` (``CbcKey.replace``) and
+        their counters restart at 0, both ordered on ``stream``."""
+        import torch
+        enc_keys, mac_keys = list(enc_keys), list(mac_keys)
+        slots = list(range(len(enc_keys))) if slots is None else [int(s) for s in slots]
+        self.table.replace(slots, enc_keys, mac_keys, stream=stream)
+        n = len(self)
+        idx = [s for s in slots if 0 <= s < n]
+        if not idx:
+            return
+        ts = stream if hasattr(stream, "cuda_stream") else (
+            torch.cuda.ExternalStream(int(stream)) if stream else torch.cuda.current_stream())
+        with torch.cuda.stream(ts):
+            at = torch.tensor(idx, dtype=torch.int64).to(self.seq_next.device, non_blocking=False)
+            self.seq_next.index_fill_(0, at, 0)
+
+    def seal(self, session, n, data, data_off, data_len, ctype, iv, wire, wire_off, wire_len,
+             seq=None, seq_out=None, stream=None):
+        seal_session_records(self.table, self.version, self.etm, session, n, data, data_off, data_len,
+                             ctype, iv, wire, wire_off, wire_len, seq=seq,
+                             seq_next=None if seq is not None else self.seq_next, seq_out=seq_out,
+                             stream=stream)
+
+    def open(self, session, n, wire, wire_off, wire_len, data, data_off, data_len, ctype, status,
+             seq=None, seq_out=None, stream=None, recv_limit=0):
+        open_session_records(self.table, self.version, self.etm, session, n, wire, wire_off, wire_len,
+                             data, data_off, data_len, ctype, status, seq=seq,
+                             seq_next=None if seq is not None else self.seq_next, seq_out=seq_out,
+                             stream=stream, recv_limit=recv_limit)
