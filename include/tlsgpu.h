@@ -437,6 +437,92 @@ typedef struct tg_rekey {
 } tg_rekey;
 int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
 
+/* TLS 1.2 key setup on the device -- the per-connection work of
+ * RecordLayer.calcPendingStates (recordlayer.py:1189-1246) and of calc_key
+ * (mathtls.py) for many sessions at once, so a TLS 1.2 session's keys never
+ * visit the host either.  TLS 1.0 / 1.1 derivation is NOT covered: their PRF
+ * is MD5 xor SHA-1 (mathtls.py:701-714) and the engine has no MD5.  A TLS 1.1
+ * CBC session still gets its rows through tg_cbc_key_replace or
+ * tg_cbc_key_replace_device, from keys derived elsewhere.
+ *
+ * tg_tls12_prf: out[i] = P_hash(secrets[i], label || seeds[i], outlen)
+ *   (mathtls.py:679-698) as PRF_1_2 (hashlen 32, SHA-256) and PRF_1_2_SHA384
+ *   (hashlen 48) use it (:716-722), for i < n, one session per lane.  secrets
+ *   (n x secretlen), seeds (n x seedlen) and out (n x outlen) are DEVICE
+ *   pointers, rows packed, any alignment; label is HOST memory and shared by
+ *   all rows.
+ *     secretlen  1 .. the hash's block size (64, SHA-384: 128); that covers the
+ *                48-byte master and premaster secrets.  A longer secret is
+ *                TG_EINVAL: HMAC would hash such a key first, which is not done
+ *                here.
+ *     labellen   at most 32; seedlen at most 128 (seeds may be NULL when 0).
+ *     outlen     1 .. 256 (the largest key block is 2 48 + 2 32 + 2 16 = 192).
+ *     n          at most 2^31.
+ *   Every argument error is TG_EINVAL before any HIP call; n == 0 is TG_OK
+ *   with nothing launched.  Nothing but out[0, n outlen) is written.  It serves
+ *   "key expansion" and "master secret" (seed from the two randoms) and
+ *   "extended master secret", "client finished" / "server finished" (seed = a
+ *   handshake hash).  The order of the randoms is the caller's business: the
+ *   reference uses server_random || client_random for "key expansion" and
+ *   client_random || server_random for "master secret" (mathtls.py:900-904).
+ *   Kernels on `stream` and library scratch only (two padded message templates
+ *   per session, holding label and seed, never the secret).
+ *
+ * tg_sessions_install_tls12 / tg_cbc_sessions_install_tls12: the TLS 1.2
+ *   counterpart of tg_sessions_rekey with TG_REKEY_INSTALL.  For list position
+ *   j and slot s = slot[j], the key block
+ *     P_hash(master_secrets[j], "key expansion" || server_random[j] ||
+ *            client_random[j])
+ *   is cut as calcPendingStates cuts it -- client MAC, server MAC, client key,
+ *   server key, client IV, server IV -- and the slices of `side` rebuild entry
+ *   s of the live handle; the raw keys exist in registers only.
+ *     AEAD handle (tg_key, every type tg_sessions_rekey covers, the single-key
+ *       AES-GCM handle included): MAC length 0, key length the handle's, IV
+ *       length fixed_iv_len: 4 for AES-GCM, AES-CCM, AES-CCM_8 and draft-00
+ *       ChaCha20, 12 for RFC 7905 ChaCha20-Poly1305 (_getCipherSettings
+ *       :1022-1079).  The IV goes to row s of iv_table (nsessions rows of
+ *       fixed_iv_len bytes, the table tg_session_records reads).
+ *     CBC handle (tg_cbc_key): the MAC key length is the handle's MAC's digest
+ *       length (20 / 32 / 48, _getMacSettings :1081-1102), the key length the
+ *       handle's; row s is rebuilt whole, as tg_cbc_key_replace_device does.
+ *       The two 16-byte IV blocks that follow in the key block are not
+ *       derived: unused at TLS >= 1.1.  fixed_iv_len and iv_table are ignored.
+ *   seq_next[s] = 0 when seq_next is given.  hashlen is the suite's PRF hash
+ *   (48 for the reference's sha384PrfSuites, else 32).  Only the pairs a
+ *   TLS 1.2 suite can produce are built: hashlen 48 goes with an AES-256-GCM
+ *   handle or an AES-256-CBC + HMAC-SHA384 handle alone, and an HMAC-SHA384
+ *   handle takes no other hashlen; any other pair is TG_EINVAL.  Everything else is
+ *   tg_sessions_rekey's contract: a slot >= nkeys is skipped (no table, IV or
+ *   counter of it read or written), the slots of one call must be DISTINCT,
+ *   ORDERING follows `stream` only (no host synchronisation, no key material
+ *   on the host), every byte of a rebuilt entry is overwritten.  Argument
+ *   errors (NULL key / struct / master_secrets / client_random /
+ *   server_random, AEAD: NULL iv_table or fixed_iv_len other than 4 / 12, bad
+ *   hashlen or side, nsessions != nkeys, n > nkeys, n > 2^31, a hashlen no
+ *   suite pairs with the handle) are TG_EINVAL before any HIP call; n == 0 is
+ *   TG_OK with nothing launched. */
+int tg_tls12_prf(int hashlen, const uint8_t* secrets, size_t secretlen, uint64_t n,
+                 const uint8_t* label, size_t labellen, const uint8_t* seeds, size_t seedlen,
+                 size_t outlen, uint8_t* out, void* stream);
+
+#define TG_TLS12_CLIENT_WRITE 0 /* the client's write keys (a server's read side) */
+#define TG_TLS12_SERVER_WRITE 1
+typedef struct tg_tls12_install {
+    uint64_t n;
+    uint32_t hashlen;           /* the suite's PRF hash: 32 or 48 */
+    uint32_t side;              /* which half of the key block */
+    uint64_t nsessions;         /* must equal the handle's nkeys */
+    const uint32_t* slot;       /* n entries, DEVICE; NULL = 0..n-1 */
+    const uint8_t* master_secrets; /* n x 48 */
+    const uint8_t* client_random;  /* n x 32 */
+    const uint8_t* server_random;  /* n x 32 */
+    uint32_t fixed_iv_len;      /* AEAD: 4 or 12; CBC: ignored */
+    uint32_t reserved;          /* ignored */
+    uint8_t* iv_table;          /* AEAD: nsessions x fixed_iv_len, required; CBC: ignored */
+    uint64_t* seq_next;         /* optional: counters of the slots set to 0 */
+} tg_tls12_install;
+int tg_sessions_install_tls12(tg_key* k, const tg_tls12_install* r, void* stream);
+
 /* TLS 1.1 / 1.2 AES-CBC + HMAC records -- the block-cipher suites of
  * RecordLayer._getCipherSettings / _getMacSettings (recordlayer.py:1056-1063,
  * :1087-1095): AES-128 / AES-256 in CBC mode with HMAC-SHA1 / -SHA256 /
@@ -548,8 +634,22 @@ int tg_cbc_open_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
  *   stream's earlier work with them, not for the device) and scrubs the
  *   staging before it returns.  n == 0 is TG_OK; NULL key or arrays, n >
  *   nkeys and a bad mackeylen are TG_EINVAL before any HIP call.  One replace
- *   at a time per handle.  (Deriving the rows on the device belongs with a
- *   TLS 1.2 PRF on the device; there is none.)
+ *   at a time per handle.
+ *
+ * tg_cbc_key_create_device / tg_cbc_key_replace_device: the same two calls
+ *   with every array in DEVICE memory, slot included (NULL = rows 0..n-1).  A
+ *   kernel builds the rows -- the forward schedule, the equivalent inverse
+ *   cipher's schedule, the two HMAC midstates -- byte for byte as the host
+ *   builds them.  tg_cbc_key_create_device synchronises `stream` before it
+ *   returns, as tg_key_create_device does; its argument errors are
+ *   tg_cbc_key_create_table's.  tg_cbc_key_replace_device has
+ *   tg_key_replace_device's contract: kernels on `stream` and nothing else, no
+ *   host synchronisation and no staging; a slot >= nkeys is skipped with
+ *   nothing read or written for it; the slots of one call must be DISTINCT;
+ *   every byte of a rebuilt row is overwritten; n == 0 is TG_OK; NULL key or
+ *   arrays, n > nkeys and a bad mackeylen are TG_EINVAL before any HIP call.
+ *   Rows derived from TLS 1.2 master secrets without the raw keys ever being
+ *   stored: tg_cbc_sessions_install_tls12 (see tg_tls12_install).
  *
  * tg_cbc_seal_session_records / tg_cbc_open_session_records.  All arrays are
  * DEVICE pointers; record i belongs to session s = session[i] and uses table
@@ -583,6 +683,11 @@ int tg_cbc_key_create_table(const uint8_t* enc_keys, size_t keylen, const uint8_
 int tg_cbc_key_info(const tg_cbc_key* k, size_t* keylen, int* mac, size_t* nkeys);
 int tg_cbc_key_replace(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys,
                        const uint8_t* mac_keys, size_t mackeylen, uint64_t n, void* stream);
+int tg_cbc_key_create_device(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys,
+                             size_t mackeylen, int mac, size_t nkeys, tg_cbc_key** out, void* stream);
+int tg_cbc_key_replace_device(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys,
+                              const uint8_t* mac_keys, size_t mackeylen, uint64_t n, void* stream);
+int tg_cbc_sessions_install_tls12(tg_cbc_key* k, const tg_tls12_install* r, void* stream);
 
 typedef struct tg_cbc_session_records {
     uint64_t n;

@@ -241,10 +241,6 @@ int launch0(int mac, const CbcKeyDev* key, const tg_cbc_records& r, bool open, h
     }
 }
 
-int mac_block(int mac) {
-    return mac == TG_MAC_SHA1 || mac == TG_MAC_SHA256 ? 64 : mac == TG_MAC_SHA384 ? 128 : 0;
-}
-
 void scrub(void* p, size_t n) {
     volatile uint8_t* v = static_cast<volatile uint8_t*>(p);
     for (size_t k = 0; k < n; ++k) v[k] = 0;
@@ -263,9 +259,7 @@ int cbc_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream, bool open)
     if (!r->data || !r->data_off || !r->data_len || !r->ctype || !r->wire || !r->wire_off || !r->wire_len)
         return fail(TG_EINVAL, "null device array");
     if (open && !r->status) return fail(TG_EINVAL, "open needs status");
-    int cur = -1;
-    HIP_TRY(hipGetDevice(&cur));
-    if (cur != k->device) HIP_TRY(hipSetDevice(k->device));
+    if (int rc = cbc_select_device(k)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return k->rounds == 10 ? launch0<10>(k->mac, k->dev_key, *r, open, s)
                            : launch0<14>(k->mac, k->dev_key, *r, open, s);
@@ -273,23 +267,6 @@ int cbc_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream, bool open)
 
 // ---- key handles: one row, or a table of them -------------------------------
 constexpr size_t kStageRows = 1024;   // tg_cbc_key_replace's pinned staging (624 KiB)
-
-const char* key_error(size_t keylen, size_t mackeylen, int mac, char (&buf)[80]) {
-    if (keylen != 16 && keylen != 32) {
-        snprintf(buf, sizeof(buf), "enc key length must be 16 or 32, got %zu", keylen);
-        return buf;
-    }
-    const int block = mac_block(mac);
-    if (!block) {
-        snprintf(buf, sizeof(buf), "unknown mac %d", mac);
-        return buf;
-    }
-    if (mackeylen == 0 || mackeylen > (size_t)block) {
-        snprintf(buf, sizeof(buf), "mac key length must be 1..%d, got %zu", block, mackeylen);
-        return buf;
-    }
-    return nullptr;
-}
 
 // The device row of one (cipher key, MAC key) pair, built on the host.
 void build_row(const uint8_t* enc_key, size_t keylen, const uint8_t* mac_key, size_t mackeylen, int mac,
@@ -311,8 +288,7 @@ int key_create(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, 
                size_t nkeys, tg_cbc_key** out) {
     if (!out || !enc_keys || !mac_keys) return fail(TG_EINVAL, "null argument");
     char buf[80];
-    if (const char* msg = key_error(keylen, mackeylen, mac, buf)) return fail(TG_EINVAL, "%s", msg);
-    if (nkeys == 0 || nkeys > 0xffffffffull) return fail(TG_EINVAL, "nkeys must be 1 .. 2^32 - 1, got %zu", nkeys);
+    if (const char* msg = table_error(keylen, mackeylen, mac, nkeys, buf)) return fail(TG_EINVAL, "%s", msg);
 
     CbcKeyDev* img = new (std::nothrow) CbcKeyDev[nkeys]();
     tg_cbc_key* k = new (std::nothrow) tg_cbc_key();
@@ -350,9 +326,7 @@ int key_create(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, 
 int key_replace(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
                 size_t mackeylen, uint64_t n, hipStream_t s) {
     const size_t keylen = k->rounds == 10 ? 16 : 32;
-    int cur = -1;
-    HIP_TRY(hipGetDevice(&cur));
-    if (cur != k->device) HIP_TRY(hipSetDevice(k->device));
+    if (int rc = cbc_select_device(k)) return rc;
     if (!k->stage) {
         HIP_TRY(hipHostMalloc((void**)&k->stage, kStageRows * sizeof(CbcKeyDev), hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&k->stage_done, hipEventDisableTiming));

@@ -1,5 +1,7 @@
-// cbc_dev.h -- what the two AES-CBC + HMAC translation units share: the key
-// handle and its device rows, the inverse-cipher tables and the equivalent
+// cbc_dev.h -- what the AES-CBC + HMAC translation units share: the key
+// handle and its device rows, the argument checks of every entry point that
+// makes or refills a handle (aes_cbc.hip from host keys, tls12.hip from device
+// keys and master secrets), the inverse-cipher tables and the equivalent
 // inverse cipher (templated on the round-key provider, like aes_round.h's
 // aes_block), and the global-memory helpers that cbc_record.h reads through.
 // aes_cbc.hip (one connection per call, round keys wave-uniform) and
@@ -10,7 +12,10 @@
 // block at 0, an open kernel Td0 / Td2 there and the inverse S-box copies
 // behind it.
 #pragma once
+#include <stdio.h>
+
 #include "aes_round.h"
+#include "api.h"
 #include "cbc_record.h"
 
 namespace tg {
@@ -42,6 +47,48 @@ struct tg_cbc_key {
 
 namespace tg {
 namespace {
+
+// ---- host side: what every entry point that takes or makes a handle checks --
+inline int mac_block(int mac) {
+    return mac == TG_MAC_SHA1 || mac == TG_MAC_SHA256 ? 64 : mac == TG_MAC_SHA384 ? 128 : 0;
+}
+
+// The text of what is wrong with a (cipher key length, MAC key length, MAC)
+// triple, or nullptr.
+inline const char* key_error(size_t keylen, size_t mackeylen, int mac, char (&buf)[80]) {
+    if (keylen != 16 && keylen != 32) {
+        snprintf(buf, sizeof(buf), "enc key length must be 16 or 32, got %zu", keylen);
+        return buf;
+    }
+    const int block = mac_block(mac);
+    if (!block) {
+        snprintf(buf, sizeof(buf), "unknown mac %d", mac);
+        return buf;
+    }
+    if (mackeylen == 0 || mackeylen > (size_t)block) {
+        snprintf(buf, sizeof(buf), "mac key length must be 1..%d, got %zu", block, mackeylen);
+        return buf;
+    }
+    return nullptr;
+}
+
+// key_error, then the row count of a new table.
+inline const char* table_error(size_t keylen, size_t mackeylen, int mac, size_t nkeys, char (&buf)[80]) {
+    if (const char* msg = key_error(keylen, mackeylen, mac, buf)) return msg;
+    if (nkeys == 0 || nkeys > 0xffffffffull) {
+        snprintf(buf, sizeof(buf), "nkeys must be 1 .. 2^32 - 1, got %zu", nkeys);
+        return buf;
+    }
+    return nullptr;
+}
+
+// Makes the handle's device the current one.
+inline int cbc_select_device(const tg_cbc_key* k) {
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != k->device) HIP_TRY(hipSetDevice(k->device));
+    return TG_OK;
+}
 
 static_assert(cbc::kRecOk == TG_REC_OK && cbc::kRecBadMac == TG_REC_BAD_MAC && cbc::kRecOverflow == TG_REC_OVERFLOW &&
                   cbc::kRecDecryptFailed == TG_REC_DECRYPT_FAILED,

@@ -423,6 +423,11 @@ int tg_launch_aes_setup(int keylen, int layout, const uint8_t* keys, uint64_t n,
 int tg_launch_rekey(int hashlen, int keylen, int layout, const tg::HkdfMsg* msgs, const uint32_t* slot,
                     const uint8_t* src, uint8_t* secrets, uint8_t* iv_table, uint64_t* seq_next, uint64_t n,
                     uint64_t nkeys, void* out, hipStream_t s);
+// The guarded chain behind a rebuilt single AES-GCM key (GcmKeyDev with rk,
+// rounds and H parked in ghash[0], as a layout-0 front kernel leaves it): the
+// GHASH tables, powers and key planes; skipped when slot names another entry
+// than 0.  For front kernels of other files (tls12.hip).
+int tg_launch_single_rebuild(void* key, const uint32_t* slot, hipStream_t s);
 int tg_launch_gather(const uint8_t* src, const uint64_t* src_off, const uint32_t* len, uint8_t* dst,
                      const uint64_t* dst_off, uint64_t n, hipStream_t s);
 int tg_launch_nonces(int mode, const uint8_t* iv_host, uint64_t seq0, uint64_t n, uint8_t* out,

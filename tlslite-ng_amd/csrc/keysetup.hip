@@ -21,16 +21,12 @@
 //                    KeyUpdate), fused: HKDF, key expansion, H and the
 //                    entry's store in one lane (tg_key_replace_device,
 //                    tg_sessions_rekey).
-#include "aes_bs8.h"
-#include "common.h"
-#include "sha.h"
+// The AES schedule, the entry store and the word helpers are keysetup_dev.h's,
+// shared with the TLS 1.2 key setup of tls12.hip.
+#include "keysetup_dev.h"
 
 namespace tg {
 namespace {
-
-__device__ __forceinline__ uint32_t be32(const uint8_t* p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
 
 template <class H>
 __device__ __forceinline__ typename H::word load_be(const uint8_t* p) {
@@ -104,140 +100,6 @@ __global__ __launch_bounds__(256) void hkdf_kernel(tg::HkdfMsg msg, const uint8_
     }
 }
 
-// ------------------------------------------------------- AES key schedule --
-constexpr uint8_t xtime8(uint8_t a) { return (uint8_t)((a << 1) ^ ((a & 0x80) ? 0x1b : 0)); }
-
-struct SboxTable {
-    uint8_t s[256];
-};
-
-constexpr SboxTable make_sbox() {
-    uint8_t exp[256] = {};
-    uint8_t log[256] = {};
-    uint8_t x = 1;
-    for (int i = 0; i < 255; ++i) {
-        exp[i] = x;
-        log[x] = (uint8_t)i;
-        x = (uint8_t)(x ^ xtime8(x));
-    }
-    SboxTable t = {};
-    for (int v = 0; v < 256; ++v) {
-        uint8_t inv = v ? exp[(255 - log[v]) % 255] : 0;
-        uint8_t s = inv, r = inv;
-        for (int k = 0; k < 4; ++k) {
-            r = (uint8_t)((r << 1) | (r >> 7));
-            s = (uint8_t)(s ^ r);
-        }
-        t.s[v] = (uint8_t)(s ^ 0x63);
-    }
-    return t;
-}
-
-__constant__ SboxTable c_sbox = make_sbox();
-
-__device__ __forceinline__ uint32_t sub_word(const uint8_t* sb, uint32_t w) {
-    return (uint32_t)sb[w & 0xff] | ((uint32_t)sb[(w >> 8) & 0xff] << 8) |
-           ((uint32_t)sb[(w >> 16) & 0xff] << 16) | ((uint32_t)sb[w >> 24] << 24);
-}
-
-// FIPS-197 key expansion (rijndael.py:922-993); words are LE words of the
-// key-schedule bytes (the layout every AES kernel reads).
-// expand_words: rk[0 .. NK) hold the key already.
-template <int NK>
-__device__ __forceinline__ void expand_words(const uint8_t* sb, uint32_t rk[60]) {
-    constexpr int NR = NK + 6, TOTAL = 4 * (NR + 1);
-    uint32_t rcon = 1;
-#pragma unroll
-    for (int k = NK; k < TOTAL; ++k) {
-        uint32_t t = rk[k - 1];
-        if (k % NK == 0) {
-            t = sub_word(sb, (t >> 8) | (t << 24)) ^ rcon;   // SubWord(RotWord(t)) ^ Rcon
-            rcon = xtime8((uint8_t)rcon);
-        } else if (NK > 6 && k % NK == 4) {
-            t = sub_word(sb, t);
-        }
-        rk[k] = rk[k - NK] ^ t;
-    }
-#pragma unroll
-    for (int k = TOTAL; k < 60; ++k) rk[k] = 0;
-}
-
-template <int NK>
-__device__ __forceinline__ void expand_key(const uint8_t* sb, const uint8_t* key, uint32_t rk[60]) {
-#pragma unroll
-    for (int k = 0; k < NK; ++k)
-        rk[k] = (uint32_t)key[4 * k] | ((uint32_t)key[4 * k + 1] << 8) |
-                ((uint32_t)key[4 * k + 2] << 16) | ((uint32_t)key[4 * k + 3] << 24);
-    expand_words<NK>(sb, rk);
-}
-
-// E_K(0^128) bytewise (SubBytes, ShiftRows, MixColumns) -> H as 4 LE words.
-template <int NR>
-__device__ __forceinline__ void aes_zero_block(const uint8_t* sb, const uint32_t rk[60], uint32_t h[4]) {
-    uint8_t s[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s[k] = (uint8_t)(rk[k >> 2] >> (8 * (k & 3)));
-#pragma unroll
-    for (int r = 1; r <= NR; ++r) {
-        uint8_t t[16];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int row = 0; row < 4; ++row) t[4 * c + row] = sb[s[4 * ((c + row) & 3) + row]];
-        if (r != NR) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                uint8_t* a = t + 4 * c;
-                const uint8_t all = (uint8_t)(a[0] ^ a[1] ^ a[2] ^ a[3]), a0 = a[0];
-                a[0] = (uint8_t)(a[0] ^ all ^ xtime8((uint8_t)(a[0] ^ a[1])));
-                a[1] = (uint8_t)(a[1] ^ all ^ xtime8((uint8_t)(a[1] ^ a[2])));
-                a[2] = (uint8_t)(a[2] ^ all ^ xtime8((uint8_t)(a[2] ^ a[3])));
-                a[3] = (uint8_t)(a[3] ^ all ^ xtime8((uint8_t)(a[3] ^ a0)));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s[k] = (uint8_t)(t[k] ^ (rk[4 * r + (k >> 2)] >> (8 * (k & 3))));
-    }
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-        h[w] = (uint32_t)s[4 * w] | ((uint32_t)s[4 * w + 1] << 8) | ((uint32_t)s[4 * w + 2] << 16) |
-               ((uint32_t)s[4 * w + 3] << 24);
-}
-
-// out layouts: 0 = GcmKeyDev (single key), 1 = GcmTableKey[n], 2 = AesKeyDev[n]
-// Entry i of ``out`` from its expanded schedule: every byte of the entry is
-// written (layout 0: rk, rounds, pad and H parked in ghash[0]; the rest of a
-// GcmKeyDev is the launcher's chain).
-template <int NK, int LAYOUT>
-__device__ __forceinline__ void store_aes_entry(const uint8_t* sb, const uint32_t rk[60], void* out, uint64_t i) {
-    constexpr int NR = NK + 6;
-    if (LAYOUT == 2) {
-        AesKeyDev* o = static_cast<AesKeyDev*>(out) + i;
-#pragma unroll
-        for (int k = 0; k < 60; ++k) o->rk[k] = rk[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o->pad[k] = 0;
-        return;
-    }
-    uint32_t h[4];
-    aes_zero_block<NR>(sb, rk, h);
-    if (LAYOUT == 1) {
-        GcmTableKey* o = static_cast<GcmTableKey*>(out) + i;
-#pragma unroll
-        for (int k = 0; k < 60; ++k) o->rk[k] = rk[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o->hn[k] = __builtin_bswap32(__builtin_bitreverse32(h[k]));
-        return;
-    }
-    GcmKeyDev* o = static_cast<GcmKeyDev*>(out);   // n == 1
-#pragma unroll
-    for (int k = 0; k < 60; ++k) o->rk[k] = rk[k];
-    o->rounds = NR;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o->pad[k] = 0;
-    o->ghash[0] = make_uint4(h[0], h[1], h[2], h[3]);   // H parked in entry (0, 0), see below
-}
-
 template <int NK, int LAYOUT>
 __global__ void aes_setup_kernel(const uint8_t* __restrict__ keys, uint64_t n, void* out) {
     __shared__ uint8_t sb[256];
@@ -271,38 +133,6 @@ struct NoHash {
 struct RekeyMsgs {
     tg::HkdfMsg upd, key, iv;
 };
-
-typedef uint32_t u32_u1 __attribute__((aligned(1)));
-
-__device__ __forceinline__ uint32_t load_u32u(const uint8_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return *(const __attribute__((address_space(1))) u32_u1*)p;
-#else
-    return 0;
-#endif
-}
-__device__ __forceinline__ void store_u32u(uint8_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    *(__attribute__((address_space(1))) u32_u1*)p = v;
-#endif
-}
-
-// The digest as big-endian 32-bit words of its bytes.
-template <class H>
-__device__ __forceinline__ void digest_words(const typename H::word st[8], uint32_t d[12]) {
-    if constexpr (sizeof(typename H::word) == 4) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) d[k] = st[k];
-#pragma unroll
-        for (int k = 8; k < 12; ++k) d[k] = 0;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            d[2 * k] = (uint32_t)(st[k] >> 32);
-            d[2 * k + 1] = (uint32_t)st[k];
-        }
-    }
-}
 
 template <class H, int NK, int LAYOUT>
 __global__ __launch_bounds__(256) void rekey_kernel(RekeyMsgs msgs, const uint32_t* __restrict__ slot,
@@ -550,3 +380,8 @@ int tg_launch_rekey(int hashlen, int alg_keylen, int layout, const tg::HkdfMsg* 
     if (layout == 0) return launch_single_chain<true>(static_cast<GcmKeyDev*>(out), slot, s);
     return TG_OK;
 }
+
+int tg_launch_single_rebuild(void* key, const uint32_t* slot, hipStream_t s) {
+    return tg::launch_single_chain<true>(static_cast<tg::GcmKeyDev*>(key), slot, s);
+}
+

@@ -1,0 +1,742 @@
+// tls12.hip -- TLS 1.2 key setup on the device: the PRF, the key block and
+// the installs of its slices into live key tables, so a TLS 1.2 session's
+// keys never visit the host (tg_tls12_prf, tg_cbc_key_create_device,
+// tg_cbc_key_replace_device, tg_sessions_install_tls12,
+// tg_cbc_sessions_install_tls12).
+//
+// Restates, one session per lane:
+//   P_hash (tlslite/mathtls.py:679-698) as PRF_1_2 / PRF_1_2_SHA384 (:716-722)
+//     call it: A(0) = label || seed, A(i) = HMAC(secret, A(i-1)),
+//     out = HMAC(secret, A(1) || A(0)) || HMAC(secret, A(2) || A(0)) || ...
+//   RecordLayer.calcPendingStates (recordlayer.py:1189-1246): the key block
+//     P_hash(master secret, "key expansion" || server_random || client_random)
+//     cut as client MAC, server MAC, client key, server key, client IV,
+//     server IV, with the lengths of _getCipherSettings / _getMacSettings.
+//
+// Layout.  Two messages are hashed again and again per session: A(0), and
+// A(i) || A(0).  prf_pack_kernel lays both out once, SHA-padded and with their
+// length fields, as big-endian words in library scratch -- word w of session
+// i at tmpl[w * n + i], so a wave reads a word of 64 sessions in one line.
+// The second template starts with a hole of one digest: A(i) is a whole number
+// of words and is spliced in from registers with compile-time indices.  The
+// templates hold label and seed only (public handshake values); the secret
+// enters as the two HMAC midstates, computed once per lane, and A(i), the
+// outputs and the raw keys of the fused installs stay in registers.  Every
+// loop's trip count depends on lengths alone, and nothing is held in an array
+// indexed at run time: no kernel here has a private segment.
+//
+// The fused installs collect the key block's words in a register window that
+// shifts down by one digest per output block (compile-time indices inside a
+// loop that is not unrolled), pick their side's slices with selects, then run
+// the AES key schedule and the entry store of keysetup_dev.h, or build a
+// CbcKeyDev row: forward schedule, the equivalent inverse cipher's schedule
+// (build_row of aes_cbc.hip) and the two HMAC midstates of the MAC key.
+#include "api.h"
+#include "cbc_dev.h"
+#include "keys.h"
+#include "keysetup_dev.h"
+#include "runtime.h"
+
+#include <new>
+
+namespace tg {
+namespace {
+
+// ---- HMAC with the key as midstates ----------------------------------------
+template <class H>
+struct Hm {
+    typename H::word in[8], out[8];
+};
+
+// key: the HMAC key as big-endian words, zero-padded to one hash block.
+template <class H>
+__device__ __forceinline__ void hm_key(const typename H::word key[16], Hm<H>& h) {
+    using W = typename H::word;
+    const W ipad = (W)0x3636363636363636ull, opad = (W)0x5c5c5c5c5c5c5c5cull;
+    W blk[16];
+    H::init(h.in);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ ipad;
+    H::compress(h.in, blk);
+    H::init(h.out);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ opad;
+    H::compress(h.out, blk);
+}
+
+// One digest as the whole message behind a key block: its padded block.
+template <class H>
+__device__ __forceinline__ void digest_block(const typename H::word d[8], typename H::word blk[16]) {
+    using W = typename H::word;
+    constexpr int dw = H::kStateOut;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = k < dw ? d[k] : W(0);
+    blk[dw] = (W)1 << (8 * sizeof(W) - 1);                  // 0x80 terminator
+    blk[15] = (W)((H::kBlock + H::kHash) * 8);              // bit length of block + digest
+}
+
+// st: the inner digest on entry, the HMAC on return.
+template <class H>
+__device__ __forceinline__ void hm_outer(const Hm<H>& h, typename H::word st[8]) {
+    typename H::word blk[16];
+    digest_block<H>(st, blk);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) st[k] = h.out[k];
+    H::compress(st, blk);
+}
+
+// st = HMAC(a), a one digest: A(i + 1) from A(i).
+template <class H>
+__device__ __forceinline__ void hm_digest(const Hm<H>& h, const typename H::word a[8], typename H::word st[8]) {
+    typename H::word blk[16];
+    digest_block<H>(a, blk);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) st[k] = h.in[k];
+    H::compress(st, blk);
+    hm_outer<H>(h, st);
+}
+
+// st = HMAC over a packed template of nb blocks (t: its word 0 for this lane,
+// words n apart).  SPLICE: the digest a replaces the hole at its front.
+template <class H, bool SPLICE>
+__device__ __forceinline__ void hm_tmpl(const Hm<H>& h, const uint32_t* __restrict__ t, uint64_t n, uint32_t nb,
+                                        const typename H::word a[8], typename H::word st[8]) {
+    using W = typename H::word;
+    W hole[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        hole[k] = a[k];
+        st[k] = h.in[k];
+    }
+    for (uint32_t b = 0; b < nb; ++b) {   // uniform: nb comes from the lengths
+        W blk[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if constexpr (sizeof(W) == 4) {
+                blk[k] = t[(uint64_t)(16 * b + k) * n];
+            } else {
+                blk[k] = ((uint64_t)t[(uint64_t)(32 * b + 2 * k) * n] << 32) | t[(uint64_t)(32 * b + 2 * k + 1) * n];
+            }
+        }
+        if (SPLICE && b == 0) {
+#pragma unroll
+            for (int k = 0; k < H::kStateOut; ++k) blk[k] = hole[k];
+        }
+        H::compress(st, blk);
+    }
+    hm_outer<H>(h, st);
+}
+
+// ---- the two message templates ---------------------------------------------
+struct PrfGeom {
+    uint32_t hashlen, block, nb1, nb2;
+    __host__ __device__ uint32_t words() const { return (nb1 + nb2) * (block / 4); }
+};
+
+PrfGeom prf_geom(int hashlen, size_t msglen) {
+    PrfGeom g;
+    g.hashlen = (uint32_t)hashlen;
+    g.block = hashlen == 32 ? 64 : 128;
+    const uint32_t lenbytes = g.block / 8;
+    g.nb1 = (uint32_t)((msglen + lenbytes) / g.block + 1);
+    g.nb2 = (uint32_t)((hashlen + msglen + lenbytes) / g.block + 1);
+    return g;
+}
+
+struct PrfPack {
+    uint32_t label[8];      // LE words of the label's bytes
+    uint32_t labellen;
+    uint32_t len0, len1;    // the seed is row i of seed0 then row i of seed1
+    const uint8_t* seed0;
+    const uint8_t* seed1;
+    PrfGeom g;
+    uint64_t n;
+    uint32_t* tmpl;
+};
+
+__global__ __launch_bounds__(256) void prf_pack_kernel(PrfPack p) {
+    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t w1 = p.g.nb1 * (p.g.block / 4), wt = p.g.words();
+    if (gid >= p.n * wt) return;
+    const uint64_t i = gid % p.n;
+    const uint32_t w = (uint32_t)(gid / p.n);
+    const bool second = w >= w1;
+    const uint32_t hole = second ? p.g.hashlen : 0u;
+    const uint32_t wi = second ? w - w1 : w, words = second ? wt - w1 : w1;
+    const uint32_t s0 = hole + p.labellen, s1 = s0 + p.len0, end = s1 + p.len1;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; ++b) {
+        const uint32_t at = 4 * wi + b;
+        uint32_t byte = 0;
+        if (at < hole) {
+            byte = 0;
+        } else if (at < s0) {
+            const uint32_t idx = at - hole;
+            uint32_t lw = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) lw = (idx >> 2) == k ? p.label[k] : lw;
+            byte = (lw >> (8 * (idx & 3))) & 0xffu;
+        } else if (at < s1) {
+            byte = ((gptr_c)p.seed0)[(uint64_t)p.len0 * i + (at - s0)];
+        } else if (at < end) {
+            byte = ((gptr_c)p.seed1)[(uint64_t)p.len1 * i + (at - s1)];
+        } else if (at == end) {
+            byte = 0x80;
+        }
+        v = (v << 8) | byte;
+    }
+    if (wi == words - 1) v = (p.g.block + end) * 8u;   // the bit length: below 2^32, the words above it stay 0
+    p.tmpl[(uint64_t)w * p.n + i] = v;
+}
+
+// ---- tg_tls12_prf ------------------------------------------------------------
+template <class H>
+__global__ __launch_bounds__(256) void tls12_prf_kernel(const uint32_t* __restrict__ tmpl, uint32_t nb1, uint32_t nb2,
+                                                        const uint8_t* __restrict__ secrets, uint32_t secretlen,
+                                                        uint64_t n, uint32_t outlen, uint8_t* __restrict__ out) {
+    using W = typename H::word;
+    constexpr int WB = sizeof(W);
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const gptr_c sec = (gptr_c)(secrets + (uint64_t)secretlen * i);
+    Hm<H> h;
+    {
+        W key[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            W v = 0;
+#pragma unroll
+            for (int b = 0; b < WB; ++b) {
+                const uint32_t at = (uint32_t)(k * WB + b);
+                uint32_t byte = 0;
+                if (at < secretlen) byte = sec[at];
+                v = (W)((v << 8) | byte);
+            }
+            key[k] = v;
+        }
+        hm_key<H>(key, h);
+    }
+    const uint32_t* t1 = tmpl + i;
+    const uint32_t* t2 = tmpl + (uint64_t)nb1 * (H::kBlock / 4) * n + i;
+    W a[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = 0;
+    hm_tmpl<H, false>(h, t1, n, nb1, a, o);                 // A(1)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = o[k];
+    const gptr op = (gptr)(out + (uint64_t)outlen * i);
+    for (uint32_t pos = 0; pos < outlen; pos += H::kHash) { // uniform
+        hm_tmpl<H, true>(h, t2, n, nb2, a, o);
+#pragma unroll
+        for (int k = 0; k < H::kHash; ++k)
+            if (pos + k < outlen) op[pos + k] = (uint8_t)(o[k / WB] >> (8 * (WB - 1 - (k % WB))));
+        if (pos + H::kHash < outlen) {
+            hm_digest<H>(h, a, o);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] = o[k];
+        }
+    }
+}
+
+// ---- the key block in registers ----------------------------------------------
+// The first NB digests of P_hash(master secret j, template) as big-endian
+// 32-bit words of the key block's bytes.
+template <class H, int NB>
+__device__ __forceinline__ void key_block(const uint32_t* __restrict__ tmpl, uint32_t nb1, uint32_t nb2,
+                                          const uint8_t* __restrict__ ms, uint64_t n, uint64_t j,
+                                          uint32_t kb[NB * (H::kHash / 4)]) {
+    using W = typename H::word;
+    constexpr int HW = H::kHash / 4;
+    Hm<H> h;
+    {
+        W key[16];   // the 48-byte master secret
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if constexpr (sizeof(W) == 4) {
+                key[k] = k < 12 ? bswap32(load_u32u(ms + 48 * j + 4 * k)) : 0u;
+            } else {
+                key[k] = k < 6 ? ((uint64_t)bswap32(load_u32u(ms + 48 * j + 8 * k)) << 32) |
+                                     bswap32(load_u32u(ms + 48 * j + 8 * k + 4))
+                               : 0ull;
+            }
+        }
+        hm_key<H>(key, h);
+    }
+    const uint32_t* t1 = tmpl + j;
+    const uint32_t* t2 = tmpl + (uint64_t)nb1 * (H::kBlock / 4) * n + j;
+    W a[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = 0;
+#pragma unroll
+    for (int k = 0; k < NB * HW; ++k) kb[k] = 0;
+    hm_tmpl<H, false>(h, t1, n, nb1, a, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = o[k];
+#pragma unroll 1
+    for (int b = 0; b < NB; ++b) {
+        hm_tmpl<H, true>(h, t2, n, nb2, a, o);
+        uint32_t d[12];
+        digest_words<H>(o, d);
+        // the window moves down one digest; after NB rounds digest 0 is at kb[0]
+#pragma unroll
+        for (int k = 0; k < (NB - 1) * HW; ++k) kb[k] = kb[k + HW];
+#pragma unroll
+        for (int k = 0; k < HW; ++k) kb[(NB - 1) * HW + k] = d[k];
+        if (b + 1 < NB) {
+            hm_digest<H>(h, a, o);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] = o[k];
+        }
+    }
+}
+
+// ---- tg_sessions_install_tls12 -----------------------------------------------
+// Lane j installs the AEAD key and fixed IV of its side into entry slot[j].
+// NK / LAYOUT as rekey_kernel's (keysetup.hip); ivw: IV words, 1 or 3.
+template <class H, int NK, int LAYOUT>
+__global__ __launch_bounds__(256) void tls12_install_kernel(const uint32_t* __restrict__ tmpl, uint32_t nb1,
+                                                            uint32_t nb2, const uint32_t* __restrict__ slot,
+                                                            const uint8_t* __restrict__ ms, uint32_t side,
+                                                            uint32_t ivw, uint8_t* __restrict__ iv_table,
+                                                            uint64_t* __restrict__ seq_next, uint64_t n,
+                                                            uint64_t nkeys, void* out) {
+    constexpr int KW = NK ? NK : 8, HW = H::kHash / 4;
+    constexpr int NEED = 2 * KW + 6, NB = (NEED + HW - 1) / HW;   // both keys, both 12-byte IVs
+    __shared__ uint8_t sb[256];
+    if (NK) {
+        for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
+        __syncthreads();
+    }
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t s = slot ? (uint64_t)slot[j] : j;
+    if (s >= nkeys) return;
+    uint32_t kb[NB * HW];
+    key_block<H, NB>(tmpl, nb1, nb2, ms, n, j, kb);
+    const bool server = side != 0, iv12 = ivw == 3;
+    // both sides' words are read as values and one is selected: a select of two
+    // addresses inside kb would keep the window in memory
+    uint32_t rk[60];   // rk[0 .. KW): the key as LE words of its bytes
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+        const uint32_t c = kb[k], sv = kb[KW + k];
+        rk[k] = bswap32(server ? sv : c);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t c = kb[2 * KW + k], s4 = kb[2 * KW + 1 + k], s12 = kb[2 * KW + 3 + k];
+        const uint32_t sv = iv12 ? s12 : s4;
+        const uint32_t v = server ? sv : c;
+        if ((uint32_t)k < ivw) store_u32u(iv_table + 4 * (uint64_t)ivw * s + 4 * k, bswap32(v));
+    }
+    if (seq_next) seq_next[s] = 0;
+    if constexpr (NK == 0) {
+        ChachaKeyDev* o = static_cast<ChachaKeyDev*>(out) + s;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o->k[k] = rk[k];
+    } else {
+        expand_words<NK>(sb, rk);
+        store_aes_entry<NK, LAYOUT>(sb, rk, out, s);
+    }
+}
+
+// ---- CBC rows ------------------------------------------------------------------
+// InvMixColumns of one column, the four bytes at once; inv_mix_column of
+// cbc_dev.h (the host's) is the definition.
+constexpr uint32_t xtime_x4(uint32_t w) { return ((w & 0x7f7f7f7fu) << 1) ^ (((w >> 7) & 0x01010101u) * 0x1bu); }
+constexpr uint32_t ror32(uint32_t w, int n) { return (w >> n) | (w << (32 - n)); }
+constexpr uint32_t inv_mix_x4(uint32_t w) {
+    const uint32_t x2 = xtime_x4(w), x4 = xtime_x4(x2), x8 = xtime_x4(x4);
+    const uint32_t m9 = x8 ^ w, mb = m9 ^ x2, md = m9 ^ x4, me = x8 ^ x4 ^ x2;
+    // b_i = 0e a_i ^ 0b a_(i+1) ^ 0d a_(i+2) ^ 09 a_(i+3), byte i of a LE word
+    return me ^ ror32(mb, 8) ^ ror32(md, 16) ^ ror32(m9, 24);
+}
+static_assert(inv_mix_x4(0x00000001u) == inv_mix_column(0x00000001u), "InvMixColumns");
+static_assert(inv_mix_x4(0x8f3c21e7u) == inv_mix_column(0x8f3c21e7u), "InvMixColumns");
+static_assert(inv_mix_x4(0xffa05b80u) == inv_mix_column(0xffa05b80u), "InvMixColumns");
+static_assert(inv_mix_x4(0x1b9d4fc6u) == inv_mix_column(0x1b9d4fc6u), "InvMixColumns");
+
+// Every byte of row o, as build_row (aes_cbc.hip) builds it on the host.
+// rk[0 .. NK): the cipher key as LE words; m: the MAC key as big-endian words,
+// zero-padded to one block of HM.
+template <int NK, class HM>
+__device__ __forceinline__ void store_cbc_row(const uint8_t* sb, uint32_t rk[60], const typename HM::word m[16],
+                                              CbcKeyDev* o, uint32_t mac) {
+    constexpr int NR = NK + 6;
+    expand_words<NK>(sb, rk);
+#pragma unroll
+    for (int k = 0; k < 60; ++k) o->ek[k] = rk[k];
+#pragma unroll
+    for (int r = 0; r <= NR; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t w = rk[4 * (NR - r) + c];
+            o->dk[4 * r + c] = (r == 0 || r == NR) ? w : inv_mix_x4(w);
+        }
+#pragma unroll
+    for (int k = 4 * (NR + 1); k < 60; ++k) o->dk[k] = 0;
+    Hm<HM> h;
+    hm_key<HM>(m, h);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        o->mid.inner[k] = (uint64_t)h.in[k];
+        o->mid.outer[k] = (uint64_t)h.out[k];
+    }
+    o->rounds = NR;
+    o->mac = mac;
+    o->pad[0] = 0;
+    o->pad[1] = 0;
+}
+
+// tg_cbc_key_create_device / tg_cbc_key_replace_device: row slot[j] from the
+// raw keys of row j.  (Named cbcrows / cbcrow, not cbc_...: the metadata test
+// of aes_cbc.hip counts that file's kernels by the pattern cbc_*_kernel.)
+template <int NK, class HM>
+__global__ __launch_bounds__(256) void cbcrows_kernel(const uint32_t* __restrict__ slot,
+                                                       const uint8_t* __restrict__ enc_keys,
+                                                       const uint8_t* __restrict__ mac_keys, uint32_t mackeylen,
+                                                       uint64_t n, uint64_t nkeys, CbcKeyDev* rows, uint32_t mac) {
+    using W = typename HM::word;
+    constexpr int WB = sizeof(W);
+    __shared__ uint8_t sb[256];
+    for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
+    __syncthreads();
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t s = slot ? (uint64_t)slot[j] : j;
+    if (s >= nkeys) return;
+    uint32_t rk[60];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) rk[k] = load_u32u(enc_keys + 4 * NK * j + 4 * k);
+    const gptr_c mk = (gptr_c)(mac_keys + (uint64_t)mackeylen * j);
+    W m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        W v = 0;
+#pragma unroll
+        for (int b = 0; b < WB; ++b) {
+            const uint32_t at = (uint32_t)(k * WB + b);
+            uint32_t byte = 0;
+            if (at < mackeylen) byte = mk[at];
+            v = (W)((v << 8) | byte);
+        }
+        m[k] = v;
+    }
+    store_cbc_row<NK, HM>(sb, rk, m, rows + s, mac);
+}
+
+// ---- tg_cbc_sessions_install_tls12 -------------------------------------------
+// HP: the suite's PRF hash; HM: the table's MAC (its digest length is the MAC
+// key's length).  The 16-byte IV blocks behind the keys are not derived: unused
+// at TLS >= 1.1.
+template <class HP, int NK, class HM>
+__global__ __launch_bounds__(256) void tls12_cbcrow_install_kernel(const uint32_t* __restrict__ tmpl, uint32_t nb1,
+                                                                uint32_t nb2, const uint32_t* __restrict__ slot,
+                                                                const uint8_t* __restrict__ ms, uint32_t side,
+                                                                uint64_t* __restrict__ seq_next, uint64_t n,
+                                                                uint64_t nkeys, CbcKeyDev* rows, uint32_t mac) {
+    using W = typename HM::word;
+    constexpr int HW = HP::kHash / 4, MW = HM::kHash / 4;
+    constexpr int NEED = 2 * MW + 2 * NK, NB = (NEED + HW - 1) / HW;
+    __shared__ uint8_t sb[256];
+    for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
+    __syncthreads();
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t s = slot ? (uint64_t)slot[j] : j;
+    if (s >= nkeys) return;
+    uint32_t kb[NB * HW];
+    key_block<HP, NB>(tmpl, nb1, nb2, ms, n, j, kb);
+    const bool server = side != 0;
+    uint32_t mk[16];   // the MAC key, big-endian 32-bit words, zero-padded
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (k < MW) {   // both sides' words as values, then the select
+            const uint32_t c = kb[k], sv = kb[MW + k];
+            mk[k] = server ? sv : c;
+        } else {
+            mk[k] = 0u;
+        }
+    }
+    uint32_t rk[60];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const uint32_t c = kb[2 * MW + k], sv = kb[2 * MW + NK + k];
+        rk[k] = bswap32(server ? sv : c);
+    }
+    W m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if constexpr (sizeof(W) == 4) {
+            m[k] = mk[k];
+        } else {
+            m[k] = k < 8 ? ((uint64_t)mk[2 * k] << 32) | mk[2 * k + 1] : 0ull;
+        }
+    }
+    if (seq_next) seq_next[s] = 0;
+    store_cbc_row<NK, HM>(sb, rk, m, rows + s, mac);
+}
+
+// ---- launchers -------------------------------------------------------------------
+bool launched() { return hipGetLastError() == hipSuccess; }
+
+unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Packs both templates of n sessions into scratch taken from sc.
+int pack_templates(int hashlen, const uint8_t* label, size_t labellen, const uint8_t* seed0, size_t len0,
+                   const uint8_t* seed1, size_t len1, uint64_t n, Scratch& sc, PrfPack* p, hipStream_t s) {
+    *p = PrfPack{};
+    for (size_t k = 0; k < labellen; ++k) p->label[k >> 2] |= (uint32_t)label[k] << (8 * (k & 3));
+    p->labellen = (uint32_t)labellen;
+    p->seed0 = seed0;
+    p->len0 = (uint32_t)len0;
+    p->seed1 = seed1;
+    p->len1 = (uint32_t)len1;
+    p->g = prf_geom(hashlen, labellen + len0 + len1);
+    p->n = n;
+    const size_t bytes = (size_t)p->g.words() * 4 * n;
+    if (int rc = sc.alloc(bytes)) return rc;
+    p->tmpl = sc.take<uint32_t>(bytes, 256);
+    const uint64_t threads = (uint64_t)p->g.words() * n;
+    hipLaunchKernelGGL(prf_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, *p);
+    return launched() ? TG_OK : TG_EHIP;
+}
+
+constexpr uint64_t kMaxSessions = 1ull << 31;   // grids of both kernels stay below 2^31 blocks
+
+const uint8_t kKeyExpansion[] = "key expansion";
+
+template <class H>
+int launch_install(tg_key* k, const PrfPack& p, const tg_tls12_install& r, hipStream_t s) {
+    const int layout = k->alg == TG_CHACHA20_POLY1305 ? 3 : is_ccm(k->alg) ? 2 : (k->nkeys > 1 ? 1 : 0);
+#define TG_INSTALL(NK, L)                                                                                   \
+    hipLaunchKernelGGL((tls12_install_kernel<H, NK, L>), dim3(blocks_of(r.n)), dim3(256), 0, s, p.tmpl,     \
+                       p.g.nb1, p.g.nb2, r.slot, r.master_secrets, r.side, r.fixed_iv_len / 4, r.iv_table,  \
+                       r.seq_next, r.n, (uint64_t)k->nkeys, k->dev_key)
+    if constexpr (H::kHash == 48) {   // aead_pair_ok: AES-256-GCM only
+        if (layout == 0) TG_INSTALL(8, 0);
+        else TG_INSTALL(8, 1);
+    } else if (layout == 3) {
+        TG_INSTALL(0, 3);
+    } else if (k->keylen == 16) {
+        if (layout == 0) TG_INSTALL(4, 0);
+        else if (layout == 1) TG_INSTALL(4, 1);
+        else TG_INSTALL(4, 2);
+    } else {
+        if (layout == 0) TG_INSTALL(8, 0);
+        else if (layout == 1) TG_INSTALL(8, 1);
+        else TG_INSTALL(8, 2);
+    }
+#undef TG_INSTALL
+    if (!launched()) return TG_EHIP;
+    if (layout == 0) return tg_launch_single_rebuild(k->dev_key, r.slot, s);
+    if (layout == 1) {   // the table's derived arrays, slot forms
+        const auto* keys = static_cast<const GcmTableKey*>(k->dev_key);
+        if (int rc = tg_launch_table_hpow(keys, r.n, table_hpow(k), s, r.slot, k->nkeys)) return rc;
+        return tg_launch_kt_planes(keys, r.n, k->rounds, table_planes(k), table_rot(k), s, r.slot, k->nkeys);
+    }
+    return TG_OK;
+}
+
+// The (PRF hash, handle) pairs a TLS 1.2 suite can produce (_getCipherSettings,
+// _getMacSettings, sha384PrfSuites): the SHA-384 PRF goes with AES-256-GCM and
+// with AES-256-CBC + HMAC-SHA384 alone, and HMAC-SHA384 with no other PRF.
+// Only these are instantiated; another pair is an argument error.
+bool aead_pair_ok(uint32_t hashlen, const tg_key* k) {
+    return hashlen == 32 || (k->alg == TG_AES_GCM && k->keylen == 32);
+}
+
+bool cbc_pair_ok(uint32_t hashlen, const tg_cbc_key* k) {
+    return hashlen == 32 ? k->mac != TG_MAC_SHA384 : (k->mac == TG_MAC_SHA384 && k->rounds == 14);
+}
+
+template <class HP, int NK, class HM>
+int launch_cbc_install(tg_cbc_key* k, const PrfPack& p, const tg_tls12_install& r, hipStream_t s) {
+#define TG_CBC_INSTALL(HM)                                                                                    \
+    hipLaunchKernelGGL((tls12_cbcrow_install_kernel<HP, NK, HM>), dim3(blocks_of(r.n)), dim3(256), 0, s, p.tmpl, \
+                       p.g.nb1, p.g.nb2, r.slot, r.master_secrets, r.side, r.seq_next, r.n,                   \
+                       (uint64_t)k->nkeys, k->dev_key, (uint32_t)k->mac)
+    TG_CBC_INSTALL(HM);
+#undef TG_CBC_INSTALL
+    return launched() ? TG_OK : TG_EHIP;
+}
+
+template <int NK>
+int launch_cbc_rows(int mac, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
+                    size_t mackeylen, uint64_t n, uint64_t nkeys, CbcKeyDev* rows, hipStream_t s) {
+#define TG_CBC_ROWS(HM)                                                                                      \
+    hipLaunchKernelGGL((cbcrows_kernel<NK, HM>), dim3(blocks_of(n)), dim3(256), 0, s, slot, enc_keys,       \
+                       mac_keys, (uint32_t)mackeylen, n, nkeys, rows, (uint32_t)mac)
+    if (mac == TG_MAC_SHA1) TG_CBC_ROWS(Sha1);
+    else if (mac == TG_MAC_SHA256) TG_CBC_ROWS(Sha256);
+    else TG_CBC_ROWS(Sha384);
+#undef TG_CBC_ROWS
+    return launched() ? TG_OK : TG_EHIP;
+}
+
+int cbc_rows(int rounds, int mac, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
+             size_t mackeylen, uint64_t n, uint64_t nkeys, CbcKeyDev* rows, hipStream_t s) {
+    return rounds == 10 ? launch_cbc_rows<4>(mac, slot, enc_keys, mac_keys, mackeylen, n, nkeys, rows, s)
+                        : launch_cbc_rows<8>(mac, slot, enc_keys, mac_keys, mackeylen, n, nkeys, rows, s);
+}
+
+// The struct's own errors, whatever the key is (tg_sessions_rekey's order).
+int install_struct_error(const tg_tls12_install* r, bool aead) {
+    if (!r) return fail(TG_EINVAL, "null tg_tls12_install");
+    if (r->hashlen != 32 && r->hashlen != 48) return fail(TG_EINVAL, "hashlen must be 32 or 48, got %u", r->hashlen);
+    if (r->side != TG_TLS12_CLIENT_WRITE && r->side != TG_TLS12_SERVER_WRITE)
+        return fail(TG_EINVAL, "side %u is neither TG_TLS12_CLIENT_WRITE nor TG_TLS12_SERVER_WRITE", r->side);
+    if (aead && r->fixed_iv_len != 4 && r->fixed_iv_len != 12)
+        return fail(TG_EINVAL, "fixed_iv_len must be 4 or 12, got %u", r->fixed_iv_len);
+    if (aead && !r->iv_table) return fail(TG_EINVAL, "null iv_table");
+    if (!r->master_secrets || !r->client_random || !r->server_random)
+        return fail(TG_EINVAL, "null master_secrets, client_random or server_random");
+    return TG_OK;
+}
+
+int install_count_error(const tg_tls12_install* r, uint64_t nkeys) {
+    if (r->nsessions != nkeys)
+        return fail(TG_EINVAL, "nsessions (%llu) must equal the key handle's nkeys (%llu)",
+                    (unsigned long long)r->nsessions, (unsigned long long)nkeys);
+    if (r->n > nkeys)
+        return fail(TG_EINVAL, "n (%llu) is above the key handle's nkeys (%llu)", (unsigned long long)r->n,
+                    (unsigned long long)nkeys);
+    if (r->n > kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
+    return TG_OK;
+}
+
+}  // namespace
+}  // namespace tg
+
+using tg::fail;
+
+extern "C" {
+
+int tg_tls12_prf(int hashlen, const uint8_t* secrets, size_t secretlen, uint64_t n, const uint8_t* label,
+                 size_t labellen, const uint8_t* seeds, size_t seedlen, size_t outlen, uint8_t* out, void* stream) {
+    if (hashlen != 32 && hashlen != 48) return fail(TG_EINVAL, "hash length must be 32 or 48");
+    const size_t block = hashlen == 32 ? 64 : 128;
+    if (secretlen == 0 || secretlen > block)
+        return fail(TG_EINVAL, "secret length must be 1..%zu, got %zu", block, secretlen);
+    if (labellen > 32) return fail(TG_EINVAL, "label length must be at most 32, got %zu", labellen);
+    if (seedlen > 128) return fail(TG_EINVAL, "seed length must be at most 128, got %zu", seedlen);
+    if (outlen == 0 || outlen > 256) return fail(TG_EINVAL, "output length must be 1..256, got %zu", outlen);
+    if (labellen && !label) return fail(TG_EINVAL, "null label");
+    if (n > tg::kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
+    if (n == 0) return TG_OK;
+    if (!secrets || !out || (seedlen && !seeds)) return fail(TG_EINVAL, "null device buffer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    tg::Scratch sc(s);
+    tg::PrfPack p;
+    int rc = tg::pack_templates(hashlen, label, labellen, seeds, seedlen, nullptr, 0, n, sc, &p, s);
+    if (rc) return fail(rc, "PRF template launch failed");
+    if (hashlen == 32)
+        hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha256>, dim3(tg::blocks_of(n)), dim3(256), 0, s, p.tmpl, p.g.nb1,
+                           p.g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
+    else
+        hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha384>, dim3(tg::blocks_of(n)), dim3(256), 0, s, p.tmpl, p.g.nb1,
+                           p.g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
+    if (!tg::launched()) return fail(TG_EHIP, "PRF launch failed");
+    rc = sc.release();
+    return rc ? fail(rc, "scratch release failed") : TG_OK;
+}
+
+int tg_cbc_key_create_device(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, size_t mackeylen,
+                             int mac, size_t nkeys, tg_cbc_key** out, void* stream) {
+    if (!out || !enc_keys || !mac_keys) return fail(TG_EINVAL, "null argument");
+    char buf[80];
+    if (const char* msg = tg::table_error(keylen, mackeylen, mac, nkeys, buf)) return fail(TG_EINVAL, "%s", msg);
+    tg_cbc_key* k = new (std::nothrow) tg_cbc_key();
+    if (!k) return fail(TG_ENOMEM, "out of host memory");
+    k->rounds = keylen == 16 ? 10 : 14;
+    k->mac = mac;
+    k->nkeys = nkeys;
+    k->dev_key = nullptr;
+    k->stage = nullptr;
+    k->stage_done = nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipGetDevice(&k->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&k->dev_key, nkeys * sizeof(tg::CbcKeyDev));
+    int rc = e == hipSuccess ? TG_OK : fail(TG_EHIP, "cbc key alloc: %s", hipGetErrorString(e));
+    if (!rc && tg::cbc_rows(k->rounds, mac, nullptr, enc_keys, mac_keys, mackeylen, nkeys, nkeys, k->dev_key, s))
+        rc = fail(TG_EHIP, "cbc key setup launch failed");
+    if (!rc && (e = hipStreamSynchronize(s)) != hipSuccess)
+        rc = fail(TG_EHIP, "cbc key setup: %s", hipGetErrorString(e));
+    if (rc) {
+        if (k->dev_key) (void)hipFree(k->dev_key);
+        delete k;
+        return rc;
+    }
+    *out = k;
+    return TG_OK;
+}
+
+int tg_cbc_key_replace_device(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys, const uint8_t* mac_keys,
+                              size_t mackeylen, uint64_t n, void* stream) {
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (n > k->nkeys)
+        return fail(TG_EINVAL, "%llu rows for a table of %zu keys", (unsigned long long)n, k->nkeys);
+    if (n == 0) return TG_OK;
+    if (!enc_keys || !mac_keys) return fail(TG_EINVAL, "null argument");
+    char buf[80];
+    if (const char* msg = tg::key_error(k->rounds == 10 ? 16 : 32, mackeylen, k->mac, buf))
+        return fail(TG_EINVAL, "%s", msg);
+    if (int rc = tg::cbc_select_device(k)) return rc;
+    if (tg::cbc_rows(k->rounds, k->mac, slot, enc_keys, mac_keys, mackeylen, n, k->nkeys, k->dev_key,
+                     static_cast<hipStream_t>(stream)))
+        return fail(TG_EHIP, "cbc key replace launch failed");
+    return TG_OK;
+}
+
+int tg_sessions_install_tls12(tg_key* k, const tg_tls12_install* r, void* stream) {
+    if (int rc = tg::install_struct_error(r, true)) return rc;
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (int rc = tg::install_count_error(r, k->nkeys)) return rc;
+    if (!tg::aead_pair_ok(r->hashlen, k))
+        return fail(TG_EINVAL, "no TLS 1.2 suite pairs the SHA-384 PRF with this handle (AES-256-GCM only)");
+    if (r->n == 0) return TG_OK;
+    if (int rc = tg::select_device(k)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    tg::Scratch sc(s);
+    tg::PrfPack p;
+    int rc = tg::pack_templates((int)r->hashlen, tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32,
+                                r->n, sc, &p, s);
+    if (!rc)
+        rc = r->hashlen == 32 ? tg::launch_install<tg::Sha256>(k, p, *r, s)
+                              : tg::launch_install<tg::Sha384>(k, p, *r, s);
+    if (rc) return fail(rc, "TLS 1.2 install launch failed");
+    rc = sc.release();
+    return rc ? fail(rc, "scratch release failed") : TG_OK;
+}
+
+int tg_cbc_sessions_install_tls12(tg_cbc_key* k, const tg_tls12_install* r, void* stream) {
+    if (int rc = tg::install_struct_error(r, false)) return rc;
+    if (!k) return fail(TG_EINVAL, "null key");
+    if (int rc = tg::install_count_error(r, k->nkeys)) return rc;
+    if (!tg::cbc_pair_ok(r->hashlen, k))
+        return fail(TG_EINVAL, "no TLS 1.2 suite pairs hashlen %u with this handle's key length and MAC", r->hashlen);
+    if (r->n == 0) return TG_OK;
+    if (int rc = tg::cbc_select_device(k)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    tg::Scratch sc(s);
+    tg::PrfPack p;
+    int rc = tg::pack_templates((int)r->hashlen, tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32,
+                                r->n, sc, &p, s);
+    if (!rc) {
+        using namespace tg;
+        if (r->hashlen == 48)
+            rc = launch_cbc_install<Sha384, 8, Sha384>(k, p, *r, s);
+        else if (k->mac == TG_MAC_SHA1)
+            rc = k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha1>(k, p, *r, s)
+                                 : launch_cbc_install<Sha256, 8, Sha1>(k, p, *r, s);
+        else
+            rc = k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha256>(k, p, *r, s)
+                                 : launch_cbc_install<Sha256, 8, Sha256>(k, p, *r, s);
+    }
+    if (rc) return fail(rc, "TLS 1.2 CBC install launch failed");
+    rc = sc.release();
+    return rc ? fail(rc, "scratch release failed") : TG_OK;
+}
+
+}  // extern "C"

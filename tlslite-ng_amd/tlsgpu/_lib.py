@@ -36,10 +36,15 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_seal_session_records", "tg_open_session_records", "tg_key_replace_device",
            "tg_sessions_rekey", "tg_cbc_key_create", "tg_cbc_key_destroy", "tg_cbc_seal_records",
            "tg_cbc_open_records", "tg_cbc_key_create_table", "tg_cbc_key_info", "tg_cbc_key_replace",
-           "tg_cbc_seal_session_records", "tg_cbc_open_session_records")
+           "tg_cbc_seal_session_records", "tg_cbc_open_session_records", "tg_tls12_prf",
+           "tg_cbc_key_create_device", "tg_cbc_key_replace_device", "tg_sessions_install_tls12",
+           "tg_cbc_sessions_install_tls12")
 
 TG_REKEY_INSTALL = 0
 TG_REKEY_UPDATE = 1
+
+TG_TLS12_CLIENT_WRITE = 0
+TG_TLS12_SERVER_WRITE = 1
 
 TG_TLS11 = 0x0302
 TG_TLS12 = 0x0303
@@ -134,6 +139,24 @@ class TgRekey(ctypes.Structure):
         ("slot", ctypes.c_void_p),
         ("new_secrets", ctypes.c_void_p),
         ("secrets", ctypes.c_void_p),
+        ("iv_table", ctypes.c_void_p),
+        ("seq_next", ctypes.c_void_p),
+    ]
+
+
+class TgTls12Install(ctypes.Structure):
+    """``struct tg_tls12_install`` (include/tlsgpu.h)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("hashlen", ctypes.c_uint32),
+        ("side", ctypes.c_uint32),
+        ("nsessions", ctypes.c_uint64),
+        ("slot", ctypes.c_void_p),
+        ("master_secrets", ctypes.c_void_p),
+        ("client_random", ctypes.c_void_p),
+        ("server_random", ctypes.c_void_p),
+        ("fixed_iv_len", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
         ("iv_table", ctypes.c_void_p),
         ("seq_next", ctypes.c_void_p),
     ]
@@ -264,6 +287,12 @@ def load():
         l.tg_cbc_key_replace.argtypes = [p, p, p, p, sz, u64, p]
         l.tg_cbc_seal_session_records.argtypes = [p, ctypes.POINTER(TgCbcSessionRecords), p]
         l.tg_cbc_open_session_records.argtypes = [p, ctypes.POINTER(TgCbcSessionRecords), p]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_tls12_prf"):
+        l.tg_tls12_prf.argtypes = [i, p, sz, u64, p, sz, p, sz, sz, p, p]
+        l.tg_cbc_key_create_device.argtypes = [p, sz, p, sz, i, sz, ctypes.POINTER(ctypes.c_void_p), p]
+        l.tg_cbc_key_replace_device.argtypes = [p, p, p, p, sz, u64, p]
+        l.tg_sessions_install_tls12.argtypes = [p, ctypes.POINTER(TgTls12Install), p]
+        l.tg_cbc_sessions_install_tls12.argtypes = [p, ctypes.POINTER(TgTls12Install), p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):

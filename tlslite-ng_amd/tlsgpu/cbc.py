@@ -74,6 +74,46 @@ class CbcKey(object):
         self.handle = h
         return self
 
+    @classmethod
+    def table_from_device(cls, enc_keys, mac_keys, mac, stream=None):
+        """``table`` with the keys already in device memory
+        (tg_cbc_key_create_device): ``enc_keys`` (n x 16 or n x 32) and
+        ``mac_keys`` (n x MAC key length) are 2-D device uint8 tensors; the
+        rows are built by a kernel on ``stream``, no key visits the host."""
+        if mac not in MACS:
+            raise ValueError("mac must be one of %s" % ", ".join(sorted(MACS)))
+        n, keylen, mackeylen = _device_rows(enc_keys, mac_keys)
+        if n == 0:
+            raise ValueError("a key table needs at least one key")
+        self = cls.__new__(cls)
+        self.mac = mac
+        self.macLength = MAC_LENGTH[mac]
+        self._lib = _lib.load()
+        self.handle = None
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.tg_cbc_key_create_device(_ptr(enc_keys, "enc_keys"), keylen,
+                                                      _ptr(mac_keys, "mac_keys"), mackeylen, MACS[mac], n,
+                                                      ctypes.byref(h), _stream(stream)))
+        self.handle = h
+        return self
+
+    def replace_device(self, slots, enc_keys, mac_keys, stream=None):
+        """``replace`` with everything in device memory
+        (tg_cbc_key_replace_device): ``slots`` is a device int32 tensor, host
+        integers (uploaded) or ``None`` (the first n entries); kernels on
+        ``stream`` and nothing else -- no host synchronisation, no staging."""
+        from .batch import _slot_list
+        n, keylen, mackeylen = _device_rows(enc_keys, mac_keys)
+        slots, ns = _slot_list(slots, n)
+        if ns != n:
+            raise ValueError("one slot per key pair")
+        if n and keylen != self._keylen():
+            raise ValueError("cipher keys must have the table's length (%d)" % self._keylen())
+        self._replace_args = (slots, enc_keys, mac_keys)   # alive until the next call at least
+        _lib.check(self._lib.tg_cbc_key_replace_device(_key(self).handle, _ptr(slots, "slots"),
+                                                       _ptr(enc_keys, "enc_keys"), _ptr(mac_keys, "mac_keys"),
+                                                       mackeylen, n, _stream(stream)))
+
     @property
     def nkeys(self):
         """Entries of the handle (1 for a key made by the constructor)."""
@@ -125,6 +165,13 @@ def _key_rows(enc_keys, mac_keys):
     if len(set(map(len, enc))) > 1 or len(set(map(len, mk))) > 1:
         raise ValueError("the keys of a table have one length (one suite per table)")
     return (b"".join(enc), len(enc[0]) if enc else 0, b"".join(mk), len(mk[0]) if mk else 0, len(enc))
+
+
+def _device_rows(enc_keys, mac_keys):
+    """``(n, keylen, mackeylen)`` of two 2-D device key tensors."""
+    if enc_keys.ndim != 2 or mac_keys.ndim != 2 or enc_keys.shape[0] != mac_keys.shape[0]:
+        raise ValueError("enc_keys and mac_keys must be 2-D with one row per session")
+    return enc_keys.shape[0], enc_keys.shape[1], mac_keys.shape[1]
 
 
 def _records(n, version, etm, seq0, data, data_off, data_len, ctype, wire, wire_off, wire_len,
@@ -233,8 +280,11 @@ class CbcSessions(object):
     records are numbered in batch order from its counter, which advances
     (``getSeqNumBytes`` per record)."""
 
-    def __init__(self, table, version, etm, seq_next=None):
+    def __init__(self, table, version, etm, seq_next=None, cipher_suite=None):
+        """``cipher_suite``: the TLS 1.2 suite of the sessions -- what
+        ``install`` derives new connections' keys by."""
         import torch
+        self.cipher_suite = cipher_suite
         if not isinstance(table, CbcKey) or table.handle is None:
             raise TypeError("table must be an open tlsgpu.CbcKey")
         n = table.nkeys
@@ -243,6 +293,53 @@ class CbcSessions(object):
         elif seq_next.numel() != n or seq_next.dtype != torch.int64:
             raise ValueError("seq_next must hold one int64 counter per key of the table")
         self.table, self.version, self.etm, self.seq_next = table, int(version), int(etm), seq_next
+
+    @classmethod
+    def from_master_secrets(cls, cipher_suite, master_secrets, client_random, server_random, side,
+                            version=_lib.TG_TLS12, etm=0, stream=None):
+        """One direction (``side``: "client" or "server" write keys) of many
+        TLS 1.2 sessions of a CBC suite from their master secrets (n x 48
+        device bytes) and randoms (n x 32 each), as calcPendingStates derives
+        them (recordlayer.py:1189-1246); counters at 0.  The raw keys exist in
+        registers only (tg_cbc_sessions_install_tls12).  TLS 1.1 keys come from
+        the MD5 / SHA-1 PRF, which is not on the device: ``version`` must be
+        TLS 1.2."""
+        import torch
+        from . import keysetup
+        alg, keylen, _, mac, maclen, _ = keysetup.tls12_suite(cipher_suite)
+        if mac is None:
+            raise ValueError("suite 0x%04x is an AEAD suite: use Sessions.from_master_secrets" % cipher_suite)
+        if int(version) != _lib.TG_TLS12:
+            raise ValueError("only TLS 1.2 keys are derived on the device")
+        n = master_secrets.numel() // 48
+        dev = master_secrets.device
+        # the blank keys and counters are filled on ``stream``, where the table
+        # build and the install that overwrite them run
+        with torch.cuda.stream(keysetup.torch_stream(stream)):
+            blank_enc = torch.zeros((n, keylen), dtype=torch.uint8, device=dev)
+            blank_mac = torch.zeros((n, maclen), dtype=torch.uint8, device=dev)
+            seq_next = torch.zeros(n, dtype=torch.int64, device=dev)
+        table = CbcKey.table_from_device(blank_enc, blank_mac, mac, stream=stream)
+        self = cls(table, version, etm, seq_next=seq_next, cipher_suite=cipher_suite)
+        self.install(None, master_secrets, client_random, server_random, side, stream=stream)
+        return self
+
+    def install(self, slots, master_secrets, client_random, server_random, side, stream=None):
+        """New TLS 1.2 connections take the sessions ``slots`` (distinct; a
+        device int32 tensor, host integers, or ``None`` = the first n): row j
+        of the three inputs belongs to ``slots[j]``; the table row is rebuilt
+        from the key block's slices of ``side`` and the counter restarts at 0,
+        in place and ordered on ``stream`` only."""
+        from . import keysetup
+        from .batch import _slot_list
+        if self.version != _lib.TG_TLS12 or self.cipher_suite not in keysetup.TLS12_SUITES:
+            raise ValueError("install needs TLS 1.2 sessions with their cipher_suite")
+        slots, n = _slot_list(slots, master_secrets.numel() // 48)
+        r = keysetup.tls12_install_args(n, keysetup.TLS12_SUITES[self.cipher_suite][5], side, len(self), slots,
+                                        master_secrets, client_random, server_random, seq_next=self.seq_next)
+        self._install_args = (slots, master_secrets, client_random, server_random)   # alive until the next call
+        k = _key(self.table)
+        _lib.check(k._lib.tg_cbc_sessions_install_tls12(k.handle, ctypes.byref(r), _stream(stream)))
 
     def __len__(self):
         return self.seq_next.numel()

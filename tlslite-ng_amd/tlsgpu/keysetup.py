@@ -14,6 +14,18 @@ sessions in one launch:
 These build new arrays and a new table.  A live ``tlsgpu.Sessions`` is updated in
 place instead (``Sessions.key_update`` / ``install``, ``tg_sessions_rekey``).
 
+TLS 1.2 (``RecordLayer.calcPendingStates``, recordlayer.py:1189-1246, and
+``calc_key``, mathtls.py:827-908):
+
+* ``tls12_prf``          -- ``PRF_1_2`` / ``PRF_1_2_SHA384`` of a batch of
+  secrets (``tg_tls12_prf``): master secret, extended master secret, Finished
+  values, key block;
+* ``tls12_key_block``    -- the six slices of every session's key block;
+* ``TLS12_SUITES``       -- what a suite id means to the two above and to
+  ``Sessions.from_master_secrets`` / ``CbcSessions.from_master_secrets``, which
+  install the slices into live tables without storing the raw keys
+  (``tg_sessions_install_tls12`` / ``tg_cbc_sessions_install_tls12``).
+
 Secrets, keys and IVs are device tensors (uint8, one row per session).
 """
 from . import _lib
@@ -30,9 +42,134 @@ TLS13_SUITES = {
 }
 
 
+def _rows(ids, *row):
+    return dict((i, row) for i in ids)
+
+
+# TLS 1.2 suites (constants.py) the engine can run: algorithm, key length,
+# fixed IV length, MAC (None for AEAD), MAC key length, PRF hash length
+# (recordlayer.py _getCipherSettings :1022-1079, _getMacSettings :1081-1102;
+# PRF hash 48 for sha384PrfSuites).  A CBC suite's "fixed IV" is the 16-byte IV
+# block of the key block, unused at TLS >= 1.1.
+TLS12_SUITES = {}
+TLS12_SUITES.update(_rows((0x009c, 0x009e, 0x00a6, 0xc02b, 0xc02d, 0xc031, 0xc02f, 0x00a2, 0x00a4),
+                          "aesgcm", 16, 4, None, 0, 32))          # *_WITH_AES_128_GCM_SHA256
+TLS12_SUITES.update(_rows((0x009d, 0x009f, 0x00a7, 0xc02c, 0xc02e, 0xc032, 0xc030, 0x00a3, 0x00a5),
+                          "aesgcm", 32, 4, None, 0, 48))          # *_WITH_AES_256_GCM_SHA384
+TLS12_SUITES.update(_rows((0xc09c, 0xc09e, 0xc0ac), "aesccm", 16, 4, None, 0, 32))
+TLS12_SUITES.update(_rows((0xc09d, 0xc09f, 0xc0ad), "aesccm", 32, 4, None, 0, 32))
+TLS12_SUITES.update(_rows((0xc0a0, 0xc0a2, 0xc0ae), "aesccm_8", 16, 4, None, 0, 32))
+TLS12_SUITES.update(_rows((0xc0a1, 0xc0a3, 0xc0af), "aesccm_8", 32, 4, None, 0, 32))
+TLS12_SUITES.update(_rows((0xcca8, 0xcca9, 0xccaa), "chacha20-poly1305", 32, 12, None, 0, 32))
+TLS12_SUITES.update(_rows((0xcca1, 0xcca2, 0xcca3), "chacha20-poly1305", 32, 4, None, 0, 32))  # draft-00
+TLS12_SUITES.update(_rows((0xc01d, 0xc01e, 0xc01f, 0x002f, 0x0033, 0x0034, 0xc009, 0xc004, 0xc00e, 0xc013,
+                           0xc018, 0x0030, 0x0032), "aescbc", 16, 16, "sha1", 20, 32))
+TLS12_SUITES.update(_rows((0x003c, 0x0067, 0x006c, 0xc023, 0xc025, 0xc029, 0xc027),
+                          "aescbc", 16, 16, "sha256", 32, 32))
+TLS12_SUITES.update(_rows((0xc020, 0xc021, 0xc022, 0x0035, 0x003a, 0x0039, 0xc00a, 0xc005, 0xc00f, 0xc014,
+                           0xc019, 0x0036, 0x0038), "aescbc", 32, 16, "sha1", 20, 32))
+TLS12_SUITES.update(_rows((0x003d, 0x006b, 0x006d), "aescbc", 32, 16, "sha256", 32, 32))
+TLS12_SUITES.update(_rows((0xc024, 0xc026, 0xc02a, 0xc028), "aescbc", 32, 16, "sha384", 48, 48))
+
+CLIENT_WRITE = _lib.TG_TLS12_CLIENT_WRITE
+SERVER_WRITE = _lib.TG_TLS12_SERVER_WRITE
+
+
 def _torch():
     import torch
     return torch
+
+
+def tls12_suite(cipher_suite):
+    """The ``TLS12_SUITES`` row of a suite id; ValueError for an id that is not in the table."""
+    try:
+        return TLS12_SUITES[cipher_suite]
+    except (KeyError, TypeError):
+        raise ValueError("cipher suite %r is not in TLS12_SUITES" % (cipher_suite,))
+
+
+def torch_stream(stream):
+    """``stream`` (None = the current one, a torch stream, or a raw handle) as a torch stream."""
+    torch = _torch()
+    if stream is None:
+        return torch.cuda.current_stream()
+    if hasattr(stream, "cuda_stream"):
+        return stream
+    return torch.cuda.ExternalStream(int(stream))
+
+
+def tls12_side(side):
+    """``side`` as TG_TLS12_CLIENT_WRITE / _SERVER_WRITE: 0 / 1 or "client" / "server"."""
+    if side in ("client", "server"):
+        return CLIENT_WRITE if side == "client" else SERVER_WRITE
+    if side in (CLIENT_WRITE, SERVER_WRITE):
+        return int(side)
+    raise ValueError('side must be "client" (0) or "server" (1)')
+
+
+def tls12_prf(secrets, label, seeds, length, hashlen, out=None, stream=None):
+    """``P_hash(secret_i, label + seed_i, length)`` (mathtls.py:679-698) for
+    every row of ``secrets`` (n x secret length device bytes) with SHA-256
+    (``hashlen`` 32, ``PRF_1_2``) or SHA-384 (48, ``PRF_1_2_SHA384``)
+    (tg_tls12_prf).  ``seeds``: n x seed length device bytes, or ``None`` for
+    an empty seed; ``label`` is host bytes shared by all rows.  Returns / fills
+    ``out`` (n x length)."""
+    torch = _torch()
+    if secrets.ndim != 2:
+        raise ValueError("secrets must be a 2-D tensor, one row per session")
+    n, secretlen = secrets.shape
+    seedlen = 0
+    if seeds is not None:
+        if seeds.ndim != 2 or seeds.shape[0] != n:
+            raise ValueError("seeds must have one row per secret")
+        seedlen = seeds.shape[1]
+    if out is None:
+        out = torch.empty((n, length), dtype=torch.uint8, device=secrets.device)
+    elif out.numel() != n * length:
+        raise ValueError("out must hold %d bytes per session" % length)
+    label = bytes(label)
+    _lib.check(_lib.load().tg_tls12_prf(hashlen, _ptr(secrets, "secrets"), secretlen, n, label or None,
+                                        len(label), _ptr(seeds, "seeds") if seedlen else None, seedlen,
+                                        length, _ptr(out, "out"), _stream(stream)))
+    return out
+
+
+def tls12_key_block(cipher_suite, master_secrets, client_random, server_random, stream=None):
+    """The key block of calcPendingStates (recordlayer.py:1202-1219) for many
+    sessions, cut into its six slices: ``(client MAC key, server MAC key,
+    client key, server key, client IV, server IV)``, device tensors of one row
+    per session (the MAC keys are n x 0 for an AEAD suite)."""
+    torch = _torch()
+    _, keylen, ivlen, _, maclen, hashlen = tls12_suite(cipher_suite)
+    with torch.cuda.stream(torch_stream(stream)):
+        # torch's own kernels (the seed rows, the output and its slices) on ``stream`` too
+        seeds = torch.cat([server_random.reshape(-1, 32), client_random.reshape(-1, 32)], dim=1).contiguous()
+        block = tls12_prf(master_secrets.reshape(-1, 48), b"key expansion", seeds,
+                          2 * (maclen + keylen + ivlen), hashlen, stream=stream)
+        out, at = [], 0
+        for size in (maclen, maclen, keylen, keylen, ivlen, ivlen):
+            out.append(block[:, at:at + size].contiguous())
+            at += size
+    return tuple(out)
+
+
+def tls12_install_args(n, hashlen, side, nsessions, slots, master_secrets, client_random, server_random,
+                       fixed_iv_len=0, iv_table=None, seq_next=None):
+    """A filled ``tg_tls12_install``; the row counts of the three inputs are checked."""
+    for what, t, width in (("master_secrets", master_secrets, 48), ("client_random", client_random, 32),
+                           ("server_random", server_random, 32)):
+        if t.numel() != n * width:
+            raise ValueError("%s must hold one %d-byte row per slot" % (what, width))
+    r = _lib.TgTls12Install()
+    r.n, r.hashlen, r.side, r.nsessions = n, hashlen, tls12_side(side), nsessions
+    r.slot = _ptr(slots, "slots")
+    r.master_secrets = _ptr(master_secrets, "master_secrets")
+    r.client_random = _ptr(client_random, "client_random")
+    r.server_random = _ptr(server_random, "server_random")
+    r.fixed_iv_len = fixed_iv_len
+    r.iv_table = _ptr(iv_table, "ivs")
+    r.seq_next = _ptr(seq_next, "seq_next")
+    return r
 
 
 def hkdf_expand_label(secrets, label, context, length, hashlen, out=None, stream=None):

@@ -41,7 +41,13 @@ class Sessions(object):
             raise ValueError("seq_next must hold one int64 counter per key of the table")
         self.table, self.ivs, self.version, self.seq_next = table, ivs, int(version), seq_next
         self.cipher_suite = cipher_suite
-        self.hashlen = keysetup.TLS13_SUITES[cipher_suite][2] if cipher_suite is not None else None
+        self.hashlen = None
+        if cipher_suite in keysetup.TLS13_SUITES:
+            self.hashlen = keysetup.TLS13_SUITES[cipher_suite][2]
+        elif cipher_suite in keysetup.TLS12_SUITES:
+            self.hashlen = keysetup.TLS12_SUITES[cipher_suite][5]   # install_tls12; _rekey refuses TLS 1.2
+        elif cipher_suite is not None:
+            raise ValueError("cipher suite 0x%04x is in neither TLS13_SUITES nor TLS12_SUITES" % cipher_suite)
         if secrets is not None:
             if self.hashlen is None:
                 raise ValueError("secrets need their cipher_suite")
@@ -61,6 +67,47 @@ class Sessions(object):
         return cls(table, ivs, records.TLS13, secrets=secrets.reshape(-1, hashlen).clone(),
                    cipher_suite=cipher_suite)
 
+    @classmethod
+    def from_master_secrets(cls, cipher_suite, master_secrets, client_random, server_random, side,
+                            stream=None):
+        """One direction (``side``: "client" or "server" write keys) of many
+        TLS 1.2 sessions of an AEAD suite from their master secrets (n x 48
+        device bytes) and randoms (n x 32 each), as calcPendingStates derives
+        them (recordlayer.py:1189-1246); IV rows of 4 or 12 bytes, counters at
+        0.  The raw keys exist in registers only (tg_sessions_install_tls12)."""
+        import torch
+        alg, keylen, ivlen, mac, _, _ = keysetup.tls12_suite(cipher_suite)
+        if mac is not None:
+            raise ValueError("suite 0x%04x is a CBC suite: use CbcSessions.from_master_secrets" % cipher_suite)
+        n = master_secrets.numel() // 48
+        dev = master_secrets.device
+        # the blank key, IV and counter tensors are filled on ``stream``, where
+        # the table build and the install that overwrite them run
+        with torch.cuda.stream(keysetup.torch_stream(stream)):
+            blank = torch.zeros((n, keylen), dtype=torch.uint8, device=dev)
+            ivs = torch.zeros((n, ivlen), dtype=torch.uint8, device=dev)
+            seq_next = torch.zeros(n, dtype=torch.int64, device=dev)
+        table = KeyTable.from_device(alg, blank, n, keylen, stream=stream)
+        self = cls(table, ivs, records.TLS12, seq_next=seq_next, cipher_suite=cipher_suite)
+        self.install_tls12(None, master_secrets, client_random, server_random, side, stream=stream)
+        return self
+
+    def install_tls12(self, slots, master_secrets, client_random, server_random, side, stream=None):
+        """New TLS 1.2 connections take the sessions ``slots`` (distinct; as
+        ``key_update`` takes them, ``None`` = the first n): row j of the three
+        inputs belongs to ``slots[j]``.  Key-table entry and fixed IV are cut
+        from the key block, the counter restarts at 0, in place and ordered on
+        ``stream`` only."""
+        if self.version != records.TLS12 or self.cipher_suite not in keysetup.TLS12_SUITES:
+            raise ValueError("install_tls12 needs TLS 1.2 Sessions with their cipher_suite")
+        slots, n = _slot_list(slots, master_secrets.numel() // 48)
+        r = keysetup.tls12_install_args(n, self.hashlen, side, self.table.nkeys, slots, master_secrets,
+                                        client_random, server_random, fixed_iv_len=self.ivs.shape[1],
+                                        iv_table=self.ivs, seq_next=self.seq_next)
+        self._rekey_args = (slots, master_secrets, client_random, server_random)   # alive until the next call
+        dk = self.table._dkey
+        _lib.check(dk._lib.tg_sessions_install_tls12(dk.handle, ctypes.byref(r), _stream(stream)))
+
     def __len__(self):
         return self.table.nkeys
 
@@ -68,9 +115,14 @@ class Sessions(object):
         """The per-session sequence counters (device int64 tensor)."""
         return self.seq_next
 
-    def _rekey(self, mode, slots, new_secrets, n, stream):
+    def _need_tls13(self):
+        """TLS 1.2 Sessions also know a PRF hash (for ``install_tls12``): they
+        must never reach the TLS 1.3 HKDF with it."""
         if self.version != records.TLS13 or self.ivs.shape[1] != 12:
             raise ValueError("rekeying derives TLS 1.3 keys and 12-byte IVs")
+
+    def _rekey(self, mode, slots, new_secrets, n, stream):
+        self._need_tls13()
         r = _lib.TgRekey()
         r.n, r.mode, r.hashlen, r.nsessions = n, mode, self.hashlen, self.table.nkeys
         r.slot = _ptr(slots, "slots")
@@ -90,6 +142,7 @@ class Sessions(object):
         _reciever install a fresh ConnectionState (recordlayer.py:1351-1375).
         In place and ordered on ``stream`` only: batches enqueued before the
         call use the old keys, batches after it the new ones."""
+        self._need_tls13()
         if self.secrets is None:
             raise ValueError("these Sessions were built without traffic secrets: nothing to advance")
         slots, n = _slot_list(slots, self.table.nkeys)
@@ -99,6 +152,7 @@ class Sessions(object):
         """New connections take the sessions ``slots``: row j of ``secrets``
         (n x hash length device bytes) is the traffic secret of ``slots[j]``;
         key, IV and counter as ``from_traffic_secrets`` gives a new session."""
+        self._need_tls13()
         if self.hashlen is None:
             raise ValueError("these Sessions have no cipher_suite: the PRF hash is unknown")
         slots, n = _slot_list(slots, secrets.numel() // self.hashlen)
