@@ -440,10 +440,48 @@ int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
 /* TLS 1.2 key setup on the device -- the per-connection work of
  * RecordLayer.calcPendingStates (recordlayer.py:1189-1246) and of calc_key
  * (mathtls.py) for many sessions at once, so a TLS 1.2 session's keys never
- * visit the host either.  TLS 1.0 / 1.1 derivation is NOT covered: their PRF
- * is MD5 xor SHA-1 (mathtls.py:701-714) and the engine has no MD5.  A TLS 1.1
- * CBC session still gets its rows through tg_cbc_key_replace or
- * tg_cbc_key_replace_device, from keys derived elsewhere.
+ * visit the host either.  TLS 1.0 / 1.1 derivation -- their PRF is
+ * P_MD5 xor P_SHA1 (mathtls.py:701-714) -- has the same two steps:
+ * tg_tls10_prf and tg_cbc_sessions_install_tls11, below.  (TLS 1.0 RECORDS
+ * stay out of scope: their implicit IV chains a connection's records.)
+ *
+ * tg_tls10_prf: out[i] = PRF(secrets[i], label, seeds[i], outlen) of
+ *   mathtls.py:701-714 for i < n, one session per lane:
+ *     P_hash(md5, S1, label || seed) xor P_hash(sha1, S2, label || seed)
+ *   byte by byte, with S1 the first and S2 the last ceil(secretlen / 2) bytes
+ *   of the secret (they share the middle byte of an odd length).  Pointers and
+ *   limits are tg_tls12_prf's: secrets, seeds and out are DEVICE pointers, rows
+ *   packed, any alignment; label is HOST memory; labellen at most 32, seedlen
+ *   at most 128, outlen 1 .. 256, n at most 2^31.  secretlen is 1 .. 128, so
+ *   either half is at most one 64-byte block and is never hashed first.  Every
+ *   argument error is TG_EINVAL before any HIP call, worded and ordered as
+ *   tg_tls12_prf's; n == 0 is TG_OK with nothing launched; nothing but
+ *   out[0, n outlen) is written.  It serves TLS 1.0 and 1.1 alike: "master
+ *   secret" (seed client_random || server_random), "key expansion", and
+ *   "extended master secret", "client finished" / "server finished" (seed =
+ *   the 36 bytes MD5(handshake) || SHA1(handshake)).  Kernels on `stream` and
+ *   library scratch only (four padded message templates per session, holding
+ *   label and seed, never the secret).
+ *
+ * tg_cbc_sessions_install_tls11: tg_cbc_sessions_install_tls12 for TLS 1.1
+ *   connections, with the same struct; hashlen, fixed_iv_len and iv_table are
+ *   IGNORED.  For list position j and slot s = slot[j] the key block
+ *     PRF(master_secrets[j], "key expansion", server_random[j] ||
+ *         client_random[j])
+ *   is cut as calcPendingStates cuts it -- client MAC (20 bytes), server MAC,
+ *   client key, server key -- and the slices of `side` rebuild row s whole
+ *   (forward schedule, the equivalent inverse cipher's schedule, the two
+ *   HMAC-SHA1 midstates); seq_next[s] = 0 when seq_next is given; the two
+ *   16-byte IV blocks that follow are not derived.  Only what a TLS 1.1 AES
+ *   suite can produce is built: the handle's MAC must be TG_MAC_SHA1 (AES-128
+ *   or AES-256); an HMAC-SHA256 / -SHA384 handle is TG_EINVAL.  The rest is
+ *   tg_cbc_sessions_install_tls12's contract word for word: a slot >= nkeys is
+ *   skipped with nothing read or written for it, the slots must be DISTINCT,
+ *   ORDERING follows `stream` only, no host synchronisation and no key
+ *   material on the host, every byte of a rebuilt row is overwritten, argument
+ *   errors (NULL struct / key / master_secrets / client_random /
+ *   server_random, bad side, nsessions != nkeys, n > nkeys, n > 2^31, the
+ *   handle's MAC) are TG_EINVAL before any HIP call, n == 0 is TG_OK.
  *
  * tg_tls12_prf: out[i] = P_hash(secrets[i], label || seeds[i], outlen)
  *   (mathtls.py:679-698) as PRF_1_2 (hashlen 32, SHA-256) and PRF_1_2_SHA384
@@ -504,12 +542,15 @@ int tg_sessions_rekey(tg_key* k, const tg_rekey* r, void* stream);
 int tg_tls12_prf(int hashlen, const uint8_t* secrets, size_t secretlen, uint64_t n,
                  const uint8_t* label, size_t labellen, const uint8_t* seeds, size_t seedlen,
                  size_t outlen, uint8_t* out, void* stream);
+int tg_tls10_prf(const uint8_t* secrets, size_t secretlen, uint64_t n, const uint8_t* label,
+                 size_t labellen, const uint8_t* seeds, size_t seedlen, size_t outlen,
+                 uint8_t* out, void* stream);
 
 #define TG_TLS12_CLIENT_WRITE 0 /* the client's write keys (a server's read side) */
 #define TG_TLS12_SERVER_WRITE 1
 typedef struct tg_tls12_install {
     uint64_t n;
-    uint32_t hashlen;           /* the suite's PRF hash: 32 or 48 */
+    uint32_t hashlen;           /* the suite's PRF hash: 32 or 48 (_tls11: ignored) */
     uint32_t side;              /* which half of the key block */
     uint64_t nsessions;         /* must equal the handle's nkeys */
     const uint32_t* slot;       /* n entries, DEVICE; NULL = 0..n-1 */
@@ -649,7 +690,8 @@ int tg_cbc_open_records(tg_cbc_key* k, const tg_cbc_records* r, void* stream);
  *   every byte of a rebuilt row is overwritten; n == 0 is TG_OK; NULL key or
  *   arrays, n > nkeys and a bad mackeylen are TG_EINVAL before any HIP call.
  *   Rows derived from TLS 1.2 master secrets without the raw keys ever being
- *   stored: tg_cbc_sessions_install_tls12 (see tg_tls12_install).
+ *   stored: tg_cbc_sessions_install_tls12, and from TLS 1.1 master secrets
+ *   tg_cbc_sessions_install_tls11 (see tg_tls12_install).
  *
  * tg_cbc_seal_session_records / tg_cbc_open_session_records.  All arrays are
  * DEVICE pointers; record i belongs to session s = session[i] and uses table
@@ -688,6 +730,7 @@ int tg_cbc_key_create_device(const uint8_t* enc_keys, size_t keylen, const uint8
 int tg_cbc_key_replace_device(tg_cbc_key* k, const uint32_t* slot, const uint8_t* enc_keys,
                               const uint8_t* mac_keys, size_t mackeylen, uint64_t n, void* stream);
 int tg_cbc_sessions_install_tls12(tg_cbc_key* k, const tg_tls12_install* r, void* stream);
+int tg_cbc_sessions_install_tls11(tg_cbc_key* k, const tg_tls12_install* r, void* stream);
 
 typedef struct tg_cbc_session_records {
     uint64_t n;

@@ -9,8 +9,9 @@
 //
 // A hash H has: word (uint32_t / uint64_t), kHash (digest bytes), kStateOut
 // (digest words), kBlock (message block bytes), kLenBytes (bytes of the
-// trailing bit-length field), init(s) and compress(s, m) with m the sixteen
-// big-endian words of one block.
+// trailing bit-length field), kBigEndian (the byte order of message words,
+// length field and digest: true for all of these, false for the MD5 of md5.h),
+// init(s) and compress(s, m) with m the sixteen big-endian words of one block.
 #pragma once
 #include <stdint.h>
 
@@ -84,6 +85,7 @@ TG_HD inline uint64_t rotr64(uint64_t x, int n) { return (x >> n) | (x << (64 - 
 struct Sha1 {
     using word = uint32_t;
     static constexpr int kHash = 20, kStateOut = 5, kBlock = 64, kLenBytes = 8;
+    static constexpr bool kBigEndian = true;
     TG_HD static void init(word s[8]) {
         s[0] = 0x67452301u; s[1] = 0xefcdab89u; s[2] = 0x98badcfeu; s[3] = 0x10325476u;
         s[4] = 0xc3d2e1f0u; s[5] = 0; s[6] = 0; s[7] = 0;
@@ -120,6 +122,7 @@ struct Sha1 {
 struct Sha256 {
     using word = uint32_t;
     static constexpr int kHash = 32, kStateOut = 8, kBlock = 64, kLenBytes = 8;
+    static constexpr bool kBigEndian = true;
     TG_HD static void init(word s[8]) {
         const word iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
                             0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
@@ -151,6 +154,7 @@ struct Sha256 {
 struct Sha384 {
     using word = uint64_t;
     static constexpr int kHash = 48, kStateOut = 6, kBlock = 128, kLenBytes = 16;
+    static constexpr bool kBigEndian = true;
     TG_HD static void init(word s[8]) {
         const word iv[8] = {0xcbbb9d5dc1059ed8ull, 0x629a292a367cd507ull, 0x9159015a3070dd17ull,
                             0x152fecd8f70e5939ull, 0x67332667ffc00b31ull, 0x8eb44a8768581511ull,

@@ -31,101 +31,16 @@
 // the AES key schedule and the entry store of keysetup_dev.h, or build a
 // CbcKeyDev row: forward schedule, the equivalent inverse cipher's schedule
 // (build_row of aes_cbc.hip) and the two HMAC midstates of the MAC key.
-#include "api.h"
-#include "cbc_dev.h"
+//
+// The HMAC, template, window and row helpers are in prf_dev.h, which tls10.hip
+// (the TLS 1.0 / 1.1 PRF) shares.
 #include "keys.h"
-#include "keysetup_dev.h"
-#include "runtime.h"
+#include "prf_dev.h"
 
 #include <new>
 
 namespace tg {
 namespace {
-
-// ---- HMAC with the key as midstates ----------------------------------------
-template <class H>
-struct Hm {
-    typename H::word in[8], out[8];
-};
-
-// key: the HMAC key as big-endian words, zero-padded to one hash block.
-template <class H>
-__device__ __forceinline__ void hm_key(const typename H::word key[16], Hm<H>& h) {
-    using W = typename H::word;
-    const W ipad = (W)0x3636363636363636ull, opad = (W)0x5c5c5c5c5c5c5c5cull;
-    W blk[16];
-    H::init(h.in);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ ipad;
-    H::compress(h.in, blk);
-    H::init(h.out);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ opad;
-    H::compress(h.out, blk);
-}
-
-// One digest as the whole message behind a key block: its padded block.
-template <class H>
-__device__ __forceinline__ void digest_block(const typename H::word d[8], typename H::word blk[16]) {
-    using W = typename H::word;
-    constexpr int dw = H::kStateOut;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = k < dw ? d[k] : W(0);
-    blk[dw] = (W)1 << (8 * sizeof(W) - 1);                  // 0x80 terminator
-    blk[15] = (W)((H::kBlock + H::kHash) * 8);              // bit length of block + digest
-}
-
-// st: the inner digest on entry, the HMAC on return.
-template <class H>
-__device__ __forceinline__ void hm_outer(const Hm<H>& h, typename H::word st[8]) {
-    typename H::word blk[16];
-    digest_block<H>(st, blk);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = h.out[k];
-    H::compress(st, blk);
-}
-
-// st = HMAC(a), a one digest: A(i + 1) from A(i).
-template <class H>
-__device__ __forceinline__ void hm_digest(const Hm<H>& h, const typename H::word a[8], typename H::word st[8]) {
-    typename H::word blk[16];
-    digest_block<H>(a, blk);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = h.in[k];
-    H::compress(st, blk);
-    hm_outer<H>(h, st);
-}
-
-// st = HMAC over a packed template of nb blocks (t: its word 0 for this lane,
-// words n apart).  SPLICE: the digest a replaces the hole at its front.
-template <class H, bool SPLICE>
-__device__ __forceinline__ void hm_tmpl(const Hm<H>& h, const uint32_t* __restrict__ t, uint64_t n, uint32_t nb,
-                                        const typename H::word a[8], typename H::word st[8]) {
-    using W = typename H::word;
-    W hole[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        hole[k] = a[k];
-        st[k] = h.in[k];
-    }
-    for (uint32_t b = 0; b < nb; ++b) {   // uniform: nb comes from the lengths
-        W blk[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if constexpr (sizeof(W) == 4) {
-                blk[k] = t[(uint64_t)(16 * b + k) * n];
-            } else {
-                blk[k] = ((uint64_t)t[(uint64_t)(32 * b + 2 * k) * n] << 32) | t[(uint64_t)(32 * b + 2 * k + 1) * n];
-            }
-        }
-        if (SPLICE && b == 0) {
-#pragma unroll
-            for (int k = 0; k < H::kStateOut; ++k) blk[k] = hole[k];
-        }
-        H::compress(st, blk);
-    }
-    hm_outer<H>(h, st);
-}
 
 // ---- the two message templates ---------------------------------------------
 struct PrfGeom {
@@ -341,54 +256,7 @@ __global__ __launch_bounds__(256) void tls12_install_kernel(const uint32_t* __re
     }
 }
 
-// ---- CBC rows ------------------------------------------------------------------
-// InvMixColumns of one column, the four bytes at once; inv_mix_column of
-// cbc_dev.h (the host's) is the definition.
-constexpr uint32_t xtime_x4(uint32_t w) { return ((w & 0x7f7f7f7fu) << 1) ^ (((w >> 7) & 0x01010101u) * 0x1bu); }
-constexpr uint32_t ror32(uint32_t w, int n) { return (w >> n) | (w << (32 - n)); }
-constexpr uint32_t inv_mix_x4(uint32_t w) {
-    const uint32_t x2 = xtime_x4(w), x4 = xtime_x4(x2), x8 = xtime_x4(x4);
-    const uint32_t m9 = x8 ^ w, mb = m9 ^ x2, md = m9 ^ x4, me = x8 ^ x4 ^ x2;
-    // b_i = 0e a_i ^ 0b a_(i+1) ^ 0d a_(i+2) ^ 09 a_(i+3), byte i of a LE word
-    return me ^ ror32(mb, 8) ^ ror32(md, 16) ^ ror32(m9, 24);
-}
-static_assert(inv_mix_x4(0x00000001u) == inv_mix_column(0x00000001u), "InvMixColumns");
-static_assert(inv_mix_x4(0x8f3c21e7u) == inv_mix_column(0x8f3c21e7u), "InvMixColumns");
-static_assert(inv_mix_x4(0xffa05b80u) == inv_mix_column(0xffa05b80u), "InvMixColumns");
-static_assert(inv_mix_x4(0x1b9d4fc6u) == inv_mix_column(0x1b9d4fc6u), "InvMixColumns");
-
-// Every byte of row o, as build_row (aes_cbc.hip) builds it on the host.
-// rk[0 .. NK): the cipher key as LE words; m: the MAC key as big-endian words,
-// zero-padded to one block of HM.
-template <int NK, class HM>
-__device__ __forceinline__ void store_cbc_row(const uint8_t* sb, uint32_t rk[60], const typename HM::word m[16],
-                                              CbcKeyDev* o, uint32_t mac) {
-    constexpr int NR = NK + 6;
-    expand_words<NK>(sb, rk);
-#pragma unroll
-    for (int k = 0; k < 60; ++k) o->ek[k] = rk[k];
-#pragma unroll
-    for (int r = 0; r <= NR; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t w = rk[4 * (NR - r) + c];
-            o->dk[4 * r + c] = (r == 0 || r == NR) ? w : inv_mix_x4(w);
-        }
-#pragma unroll
-    for (int k = 4 * (NR + 1); k < 60; ++k) o->dk[k] = 0;
-    Hm<HM> h;
-    hm_key<HM>(m, h);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        o->mid.inner[k] = (uint64_t)h.in[k];
-        o->mid.outer[k] = (uint64_t)h.out[k];
-    }
-    o->rounds = NR;
-    o->mac = mac;
-    o->pad[0] = 0;
-    o->pad[1] = 0;
-}
-
+// ---- CBC rows (store_cbc_row: prf_dev.h) ----------------------------------------
 // tg_cbc_key_create_device / tg_cbc_key_replace_device: row slot[j] from the
 // raw keys of row j.  (Named cbcrows / cbcrow, not cbc_...: the metadata test
 // of aes_cbc.hip counts that file's kernels by the pattern cbc_*_kernel.)
@@ -479,10 +347,6 @@ __global__ __launch_bounds__(256) void tls12_cbcrow_install_kernel(const uint32_
 }
 
 // ---- launchers -------------------------------------------------------------------
-bool launched() { return hipGetLastError() == hipSuccess; }
-
-unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 // Packs both templates of n sessions into scratch taken from sc.
 int pack_templates(int hashlen, const uint8_t* label, size_t labellen, const uint8_t* seed0, size_t len0,
                    const uint8_t* seed1, size_t len1, uint64_t n, Scratch& sc, PrfPack* p, hipStream_t s) {
@@ -502,10 +366,6 @@ int pack_templates(int hashlen, const uint8_t* label, size_t labellen, const uin
     hipLaunchKernelGGL(prf_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, *p);
     return launched() ? TG_OK : TG_EHIP;
 }
-
-constexpr uint64_t kMaxSessions = 1ull << 31;   // grids of both kernels stay below 2^31 blocks
-
-const uint8_t kKeyExpansion[] = "key expansion";
 
 template <class H>
 int launch_install(tg_key* k, const PrfPack& p, const tg_tls12_install& r, hipStream_t s) {
@@ -579,31 +439,6 @@ int cbc_rows(int rounds, int mac, const uint32_t* slot, const uint8_t* enc_keys,
              size_t mackeylen, uint64_t n, uint64_t nkeys, CbcKeyDev* rows, hipStream_t s) {
     return rounds == 10 ? launch_cbc_rows<4>(mac, slot, enc_keys, mac_keys, mackeylen, n, nkeys, rows, s)
                         : launch_cbc_rows<8>(mac, slot, enc_keys, mac_keys, mackeylen, n, nkeys, rows, s);
-}
-
-// The struct's own errors, whatever the key is (tg_sessions_rekey's order).
-int install_struct_error(const tg_tls12_install* r, bool aead) {
-    if (!r) return fail(TG_EINVAL, "null tg_tls12_install");
-    if (r->hashlen != 32 && r->hashlen != 48) return fail(TG_EINVAL, "hashlen must be 32 or 48, got %u", r->hashlen);
-    if (r->side != TG_TLS12_CLIENT_WRITE && r->side != TG_TLS12_SERVER_WRITE)
-        return fail(TG_EINVAL, "side %u is neither TG_TLS12_CLIENT_WRITE nor TG_TLS12_SERVER_WRITE", r->side);
-    if (aead && r->fixed_iv_len != 4 && r->fixed_iv_len != 12)
-        return fail(TG_EINVAL, "fixed_iv_len must be 4 or 12, got %u", r->fixed_iv_len);
-    if (aead && !r->iv_table) return fail(TG_EINVAL, "null iv_table");
-    if (!r->master_secrets || !r->client_random || !r->server_random)
-        return fail(TG_EINVAL, "null master_secrets, client_random or server_random");
-    return TG_OK;
-}
-
-int install_count_error(const tg_tls12_install* r, uint64_t nkeys) {
-    if (r->nsessions != nkeys)
-        return fail(TG_EINVAL, "nsessions (%llu) must equal the key handle's nkeys (%llu)",
-                    (unsigned long long)r->nsessions, (unsigned long long)nkeys);
-    if (r->n > nkeys)
-        return fail(TG_EINVAL, "n (%llu) is above the key handle's nkeys (%llu)", (unsigned long long)r->n,
-                    (unsigned long long)nkeys);
-    if (r->n > kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
-    return TG_OK;
 }
 
 }  // namespace

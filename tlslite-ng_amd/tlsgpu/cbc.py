@@ -301,15 +301,18 @@ class CbcSessions(object):
         TLS 1.2 sessions of a CBC suite from their master secrets (n x 48
         device bytes) and randoms (n x 32 each), as calcPendingStates derives
         them (recordlayer.py:1189-1246); counters at 0.  The raw keys exist in
-        registers only (tg_cbc_sessions_install_tls12).  TLS 1.1 keys come from
-        the MD5 / SHA-1 PRF, which is not on the device: ``version`` must be
-        TLS 1.2."""
+        registers only (tg_cbc_sessions_install_tls12).  With ``version``
+        TLS 1.1 the keys come from the MD5 xor SHA-1 PRF
+        (tg_cbc_sessions_install_tls11), for the HMAC-SHA1 suites with AES-128
+        / AES-256; any other suite at TLS 1.1 is a ValueError."""
         import torch
         from . import keysetup
         alg, keylen, _, mac, maclen, _ = keysetup.tls12_suite(cipher_suite)
         if mac is None:
             raise ValueError("suite 0x%04x is an AEAD suite: use Sessions.from_master_secrets" % cipher_suite)
-        if int(version) != _lib.TG_TLS12:
+        if int(version) == _lib.TG_TLS11:
+            keysetup.tls11_suite(cipher_suite)
+        elif int(version) != _lib.TG_TLS12:
             raise ValueError("only TLS 1.2 keys are derived on the device")
         n = master_secrets.numel() // 48
         dev = master_secrets.device
@@ -325,21 +328,26 @@ class CbcSessions(object):
         return self
 
     def install(self, slots, master_secrets, client_random, server_random, side, stream=None):
-        """New TLS 1.2 connections take the sessions ``slots`` (distinct; a
+        """New connections of the sessions' version (TLS 1.2, or TLS 1.1 for
+        an HMAC-SHA1 suite) take the sessions ``slots`` (distinct; a
         device int32 tensor, host integers, or ``None`` = the first n): row j
         of the three inputs belongs to ``slots[j]``; the table row is rebuilt
         from the key block's slices of ``side`` and the counter restarts at 0,
         in place and ordered on ``stream`` only."""
         from . import keysetup
         from .batch import _slot_list
-        if self.version != _lib.TG_TLS12 or self.cipher_suite not in keysetup.TLS12_SUITES:
+        tls11 = self.version == _lib.TG_TLS11 and self.cipher_suite is not None
+        if tls11:
+            keysetup.tls11_suite(self.cipher_suite)
+        elif self.version != _lib.TG_TLS12 or self.cipher_suite not in keysetup.TLS12_SUITES:
             raise ValueError("install needs TLS 1.2 sessions with their cipher_suite")
         slots, n = _slot_list(slots, master_secrets.numel() // 48)
         r = keysetup.tls12_install_args(n, keysetup.TLS12_SUITES[self.cipher_suite][5], side, len(self), slots,
                                         master_secrets, client_random, server_random, seq_next=self.seq_next)
         self._install_args = (slots, master_secrets, client_random, server_random)   # alive until the next call
         k = _key(self.table)
-        _lib.check(k._lib.tg_cbc_sessions_install_tls12(k.handle, ctypes.byref(r), _stream(stream)))
+        fn = k._lib.tg_cbc_sessions_install_tls11 if tls11 else k._lib.tg_cbc_sessions_install_tls12
+        _lib.check(fn(k.handle, ctypes.byref(r), _stream(stream)))
 
     def __len__(self):
         return self.seq_next.numel()

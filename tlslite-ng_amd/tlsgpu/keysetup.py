@@ -26,6 +26,14 @@ TLS 1.2 (``RecordLayer.calcPendingStates``, recordlayer.py:1189-1246, and
   install the slices into live tables without storing the raw keys
   (``tg_sessions_install_tls12`` / ``tg_cbc_sessions_install_tls12``).
 
+TLS 1.0 / 1.1 (``PRF``, mathtls.py:701-714: P_MD5 xor P_SHA1):
+
+* ``tls10_prf``          -- the PRF of a batch of secrets (``tg_tls10_prf``);
+* ``tls11_key_block``    -- both sides' MAC key and cipher key for the
+  HMAC-SHA1 AES-CBC suites; ``CbcSessions.from_master_secrets(...,
+  version=TLS11)`` installs them without storing the raw keys
+  (``tg_cbc_sessions_install_tls11``).
+
 Secrets, keys and IVs are device tensors (uint8, one row per session).
 """
 from . import _lib
@@ -148,6 +156,64 @@ def tls12_key_block(cipher_suite, master_secrets, client_random, server_random, 
                           2 * (maclen + keylen + ivlen), hashlen, stream=stream)
         out, at = [], 0
         for size in (maclen, maclen, keylen, keylen, ivlen, ivlen):
+            out.append(block[:, at:at + size].contiguous())
+            at += size
+    return tuple(out)
+
+
+def tls10_prf(secrets, label, seeds, length, out=None, stream=None):
+    """``PRF(secret_i, label, seed_i, length)`` of TLS 1.0 / 1.1 (mathtls.py:701-714:
+    P_MD5 over the secret's first half xor P_SHA1 over its last half) for every
+    row of ``secrets`` (n x secret length device bytes, 1..128) (tg_tls10_prf).
+    ``seeds``: n x seed length device bytes, or ``None`` for an empty seed;
+    ``label`` is host bytes shared by all rows.  Returns / fills ``out``
+    (n x length)."""
+    torch = _torch()
+    if secrets.ndim != 2:
+        raise ValueError("secrets must be a 2-D tensor, one row per session")
+    n, secretlen = secrets.shape
+    seedlen = 0
+    if seeds is not None:
+        if seeds.ndim != 2 or seeds.shape[0] != n:
+            raise ValueError("seeds must have one row per secret")
+        seedlen = seeds.shape[1]
+    if out is None:
+        out = torch.empty((n, length), dtype=torch.uint8, device=secrets.device)
+    elif out.numel() != n * length:
+        raise ValueError("out must hold %d bytes per session" % length)
+    label = bytes(label)
+    _lib.check(_lib.load().tg_tls10_prf(_ptr(secrets, "secrets"), secretlen, n, label or None, len(label),
+                                        _ptr(seeds, "seeds") if seedlen else None, seedlen, length,
+                                        _ptr(out, "out"), _stream(stream)))
+    return out
+
+
+def tls11_suite(cipher_suite):
+    """``(key length, MAC key length)`` of a suite the engine runs at TLS 1.1:
+    the HMAC-SHA1 AES-CBC rows of ``TLS12_SUITES`` (the ids are the same at
+    both versions; the version picks the PRF).  ValueError, naming the suite,
+    for any other."""
+    row = TLS12_SUITES.get(cipher_suite) if isinstance(cipher_suite, int) else None
+    if row is None or row[0] != "aescbc" or row[3] != "sha1":
+        raise ValueError("cipher suite %s is not an AES-CBC + HMAC-SHA1 suite: no TLS 1.1 keys for it"
+                         % ("0x%04x" % cipher_suite if isinstance(cipher_suite, int) else repr(cipher_suite)))
+    return row[1], row[4]
+
+
+def tls11_key_block(cipher_suite, master_secrets, client_random, server_random, stream=None):
+    """The key block of calcPendingStates (recordlayer.py:1202-1219) at TLS 1.1
+    for many sessions of an HMAC-SHA1 AES-CBC suite, cut into ``(client MAC
+    key, server MAC key, client key, server key)``, device tensors of one row
+    per session.  The two IV blocks that follow are unused at TLS 1.1 and not
+    derived."""
+    torch = _torch()
+    keylen, maclen = tls11_suite(cipher_suite)
+    with torch.cuda.stream(torch_stream(stream)):
+        seeds = torch.cat([server_random.reshape(-1, 32), client_random.reshape(-1, 32)], dim=1).contiguous()
+        block = tls10_prf(master_secrets.reshape(-1, 48), b"key expansion", seeds, 2 * (maclen + keylen),
+                          stream=stream)
+        out, at = [], 0
+        for size in (maclen, maclen, keylen, keylen):
             out.append(block[:, at:at + size].contiguous())
             at += size
     return tuple(out)
