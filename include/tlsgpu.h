@@ -564,6 +564,83 @@ typedef struct tg_tls12_install {
 } tg_tls12_install;
 int tg_sessions_install_tls12(tg_key* k, const tg_tls12_install* r, void* stream);
 
+/* The TLS 1.3 key schedule on the device -- what tlsconnection.py runs per
+ * connection with hashlib (:3036-3050, :3203-3224, :3326-3360; the client at
+ * :1319-1333, :1552-1568, :1659-1701), for many sessions at once: from the
+ * (EC)DHE shared secret, an optional PSK and the transcript hashes to the
+ * traffic secrets that tg_sessions_rekey (TG_REKEY_INSTALL) installs, with the
+ * Finished values and the PSK binders on the way.  One session per lane; every
+ * secret between a call's inputs and its outputs exists in registers only.
+ *
+ * Common to the five calls.  hashlen is 32 (SHA-256) or 48 (SHA-384) and is
+ * the size of every secret, salt and transcript-hash row.  All pointers are
+ * DEVICE pointers except `label`, which is HOST memory; rows are packed (row i
+ * at rowlen * i) and may have any alignment.  n is at most 2^31; n == 0 is
+ * TG_OK with nothing launched.  Every argument error (the ones named below, a
+ * bad hashlen, n above 2^31, a NULL array that is not optional) is TG_EINVAL
+ * with a tg_last_error() reason before any HIP call, length errors first and
+ * NULL device arrays after the n == 0 shortcut, as tg_tls12_prf.  Kernels on
+ * `stream` only, no host synchronisation, no scratch; nothing is written but
+ * [0, n * rowlen) of the named outputs.
+ *
+ * tg_hkdf_extract: out[i] = HKDF-Extract(salts[i], ikm[i]) =
+ *   HMAC-Hash(salt, ikm) (secureHMAC, cryptomath.py:128-132).  salts: n x
+ *   hashlen, NULL = hashlen zero bytes for every row.  ikm: n x ikmlen with
+ *   ikmlen 1 .. 1024 (every group's shared secret up to ffdhe8192, any
+ *   external PSK); NULL = hashlen zero bytes for every row, and ikmlen must
+ *   then be 0 or hashlen.  out: n x hashlen.  The IKM is hashed in as many
+ *   blocks as ikmlen needs.
+ * tg_hkdf_expand_label_rows: tg_hkdf_expand_label with one context per row:
+ *   out[i] = HKDF-Expand-Label(secrets[i], label, contexts[i], outlen)
+ *   (cryptomath.py:155-173).  label comes without the "tls13 " prefix,
+ *   labellen at most 32; contexts: n x ctxlen, ctxlen 0 .. 64; outlen 1 ..
+ *   hashlen, out: n x outlen.  contexts == NULL with ctxlen == hashlen means
+ *   Hash("") for every row (derive_secret's handshake_hashes None, :175-195);
+ *   contexts may otherwise be NULL only when ctxlen is 0.  Derive-Secret is
+ *   the case ctxlen == outlen == hashlen with a transcript hash per row.
+ * tg_tls13_finished: out[i] = HMAC(HKDF-Expand-Label(secrets[i], "finished",
+ *   "", hashlen), hashes[i]) -- the verify_data of Finished (:3210-3216) and,
+ *   over a binder key, the PSK binder (handshakehelpers.py:44-61).  secrets,
+ *   hashes and out: n x hashlen.  The finished key is never stored.
+ * tg_tls13_handshake_secrets (tlsconnection.py:3036-3050), fused:
+ *     early   = Extract(0, psk[i])               psk NULL: hashlen zero bytes
+ *     derived = Derive-Secret(early, "derived", Hash(""))
+ *     hs      = Extract(derived, shared[i])      shared: n x sharedlen, 1 .. 1024
+ *   handshake_secret[i] = hs, client_traffic[i] = Derive-Secret(hs,
+ *   "c hs traffic", hello_hash[i]), server_traffic[i] = Derive-Secret(hs,
+ *   "s hs traffic", hello_hash[i]).  psk: n x hashlen (a PSK of the suite's
+ *   hash, as the reference's) or NULL; hello_hash: n x hashlen, the transcript
+ *   through ServerHello.  Each of the three outputs (n x hashlen) may be NULL:
+ *   not written; all three NULL is an error.
+ * tg_tls13_application_secrets (:3218-3224, :3326), fused:
+ *     derived = Derive-Secret(handshake_secret[i], "derived", Hash(""))
+ *     master  = Extract(derived, hashlen zero bytes)
+ *   master_secret[i] = master and, all over finished_hash[i] (the transcript
+ *   through the server's Finished), client_traffic[i] = Derive-Secret(master,
+ *   "c ap traffic"), server_traffic[i] = ... "s ap traffic",
+ *   exporter_master[i] = ... "exp master".  Each of the four outputs may be
+ *   NULL: not written; all four NULL is an error.  master_secret may EQUAL
+ *   handshake_secret: a lane has read its whole input row before its first
+ *   store, so the handshake secrets are overwritten in place.  Any other
+ *   overlap of an output's [0, n * hashlen) with an input's or with another
+ *   output's is TG_EINVAL.  ("res master" needs the client's Finished in the
+ *   transcript: tg_hkdf_expand_label_rows on master_secret, later.)
+ * Expand-Label outputs longer than one digest (the exporter's last step) are
+ * out of scope. */
+int tg_hkdf_extract(int hashlen, const uint8_t* salts, const uint8_t* ikm, size_t ikmlen,
+                    uint64_t n, uint8_t* out, void* stream);
+int tg_hkdf_expand_label_rows(int hashlen, const uint8_t* secrets, uint64_t n, const uint8_t* label,
+                              size_t labellen, const uint8_t* contexts, size_t ctxlen, size_t outlen,
+                              uint8_t* out, void* stream);
+int tg_tls13_finished(int hashlen, const uint8_t* secrets, const uint8_t* hashes, uint64_t n,
+                      uint8_t* out, void* stream);
+int tg_tls13_handshake_secrets(int hashlen, const uint8_t* psk, const uint8_t* shared, size_t sharedlen,
+                               const uint8_t* hello_hash, uint64_t n, uint8_t* handshake_secret,
+                               uint8_t* client_traffic, uint8_t* server_traffic, void* stream);
+int tg_tls13_application_secrets(int hashlen, const uint8_t* handshake_secret, const uint8_t* finished_hash,
+                                 uint64_t n, uint8_t* master_secret, uint8_t* client_traffic,
+                                 uint8_t* server_traffic, uint8_t* exporter_master, void* stream);
+
 /* TLS 1.1 / 1.2 AES-CBC + HMAC records -- the block-cipher suites of
  * RecordLayer._getCipherSettings / _getMacSettings (recordlayer.py:1056-1063,
  * :1087-1095): AES-128 / AES-256 in CBC mode with HMAC-SHA1 / -SHA256 /

@@ -1,6 +1,7 @@
 // keysetup_dev.h -- device functions the key-setup translation units share
 // (keysetup.hip: TLS 1.3 derivation and rekey; tls12.hip: the TLS 1.2 PRF, its
-// fused installs and the CBC rows): the AES key schedule and the per-layout
+// fused installs and the CBC rows; tls13.hip: the TLS 1.3 key schedule): HKDF's
+// T(1) over a shared message, the AES key schedule and the per-layout
 // entry store, H = E_K(0), unaligned word access and the digest as 32-bit
 // words.  Everything sits in an anonymous namespace: each translation unit
 // has its own copy, kernels are launched from the file that defines them.
@@ -14,6 +15,61 @@ namespace {
 
 __device__ __forceinline__ uint32_t be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+// ------------------------------------------------------- HKDF-Expand T(1) --
+// (keysetup.hip: hkdf_kernel, rekey_kernel; tls13.hip: the steps of the key
+// schedule whose HkdfLabel is the same for every session.)
+template <class H>
+__device__ __forceinline__ typename H::word load_be(const uint8_t* p) {
+    if constexpr (sizeof(typename H::word) == 4) {
+        return be32(p);
+    } else {
+        return ((uint64_t)be32(p) << 32) | be32(p + 4);
+    }
+}
+
+// HMAC(secret, info || 0x01): HKDF_expand's first block T(1)
+// (cryptomath.py:146-153), which is all of it for outlen <= hash length.
+// key: the secret as big-endian words, zero-padded to one hash block; st
+// receives the digest words.
+template <class H>
+__device__ __forceinline__ void hkdf_t1(const tg::HkdfMsg& msg, const typename H::word key[16],
+                                        typename H::word st[8]) {
+    using W = typename H::word;
+    constexpr int WB = sizeof(W);
+    const W ipad = (W)0x3636363636363636ull, opad = (W)0x5c5c5c5c5c5c5c5cull;
+    W blk[16];
+    // inner: H((K ^ ipad) || info || 0x01)
+    H::init(st);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ ipad;
+    H::compress(st, blk);
+    for (uint32_t b = 0; b < msg.nblocks; ++b) {   // uniform message blocks
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if constexpr (WB == 4) {
+                blk[k] = msg.words[16 * b + k];
+            } else {
+                blk[k] = ((uint64_t)msg.words[32 * b + 2 * k] << 32) | msg.words[32 * b + 2 * k + 1];
+            }
+        }
+        H::compress(st, blk);
+    }
+    // outer: H((K ^ opad) || inner digest), one padded block
+    W inner[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) inner[k] = st[k];
+    H::init(st);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ opad;
+    H::compress(st, blk);
+    constexpr int dw = H::kStateOut;                       // digest words
+#pragma unroll
+    for (int k = 0; k < 16; ++k) blk[k] = k < dw ? inner[k] : W(0);
+    blk[dw] = (W)1 << (8 * WB - 1);                        // 0x80 terminator
+    blk[15] = (W)((16 * WB + H::kHash) * 8);               // bit length of block + digest
+    H::compress(st, blk);
 }
 
 // ------------------------------------------------------- AES key schedule --

@@ -38,7 +38,9 @@ EXPORTS = ("tg_version", "tg_last_error", "tg_device_count", "tg_init", "tg_key_
            "tg_cbc_open_records", "tg_cbc_key_create_table", "tg_cbc_key_info", "tg_cbc_key_replace",
            "tg_cbc_seal_session_records", "tg_cbc_open_session_records", "tg_tls12_prf",
            "tg_cbc_key_create_device", "tg_cbc_key_replace_device", "tg_sessions_install_tls12",
-           "tg_cbc_sessions_install_tls12", "tg_tls10_prf", "tg_cbc_sessions_install_tls11")
+           "tg_cbc_sessions_install_tls12", "tg_tls10_prf", "tg_cbc_sessions_install_tls11",
+           "tg_hkdf_extract", "tg_hkdf_expand_label_rows", "tg_tls13_finished",
+           "tg_tls13_handshake_secrets", "tg_tls13_application_secrets")
 
 TG_REKEY_INSTALL = 0
 TG_REKEY_UPDATE = 1
@@ -296,6 +298,12 @@ def load():
     if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_tls10_prf"):
         l.tg_tls10_prf.argtypes = [p, sz, u64, p, sz, p, sz, sz, p, p]
         l.tg_cbc_sessions_install_tls11.argtypes = [p, ctypes.POINTER(TgTls12Install), p]
+    if os.environ.get("TLSGPU_LIB") is None or hasattr(l, "tg_hkdf_extract"):
+        l.tg_hkdf_extract.argtypes = [i, p, p, sz, u64, p, p]
+        l.tg_hkdf_expand_label_rows.argtypes = [i, p, u64, p, sz, p, sz, sz, p, p]
+        l.tg_tls13_finished.argtypes = [i, p, p, u64, p, p]
+        l.tg_tls13_handshake_secrets.argtypes = [i, p, p, sz, p, u64, p, p, p, p]
+        l.tg_tls13_application_secrets.argtypes = [i, p, p, u64, p, p, p, p, p]
     for name in EXPORTS:
         if name not in ("tg_version", "tg_last_error"):
             if os.environ.get("TLSGPU_LIB") is not None and not hasattr(l, name):

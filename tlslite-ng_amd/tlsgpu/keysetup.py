@@ -14,6 +14,30 @@ sessions in one launch:
 These build new arrays and a new table.  A live ``tlsgpu.Sessions`` is updated in
 place instead (``Sessions.key_update`` / ``install``, ``tg_sessions_rekey``).
 
+The TLS 1.3 key schedule above the traffic secrets (tlsconnection.py:3036-3050,
+:3203-3224, :3326-3360; the client at :1319-1333, :1552-1568, :1659-1701), from
+the (EC)DHE shared secret, an optional PSK and the transcript hashes:
+
+* ``hkdf_extract``       -- ``secureHMAC(salt, ikm)`` (cryptomath.py:128-132),
+  HKDF-Extract, of a batch (``tg_hkdf_extract``);
+* ``hkdf_expand_label_rows`` / ``derive_secret`` -- ``HKDF_expand_label`` with a
+  context per session, and ``derive_secret`` (:175-195), its case of one
+  transcript hash per session (``tg_hkdf_expand_label_rows``);
+* ``tls13_finished``     -- the Finished verify_data of every session
+  (``tg_tls13_finished``);
+* ``tls13_handshake_secrets`` -- early secret, "derived", handshake secret and
+  both handshake traffic secrets in one launch
+  (``tg_tls13_handshake_secrets``); ``Sessions.install_handshake`` installs
+  one side's keys from them;
+* ``tls13_application_secrets`` -- "derived", master secret, both application
+  traffic secrets and the exporter master secret in one launch
+  (``tg_tls13_application_secrets``); ``Sessions.install_application``;
+* ``tls13_binders`` / ``tls13_resumption_psk`` -- the PSK binder of
+  ``HandshakeHelpers._calc_binder`` (handshakehelpers.py:44-61) and the
+  ticket PSK of ``calc_res_binder_psk`` (:64-72).
+
+Every secret between a call's inputs and its outputs stays in registers.
+
 TLS 1.2 (``RecordLayer.calcPendingStates``, recordlayer.py:1189-1246, and
 ``calc_key``, mathtls.py:827-908):
 
@@ -270,3 +294,166 @@ def key_update(cipher_suite, secrets, stream=None):
     recordlayer.py:1333-1336): HKDF-Expand-Label(secret, "traffic upd", "", Hash.length)."""
     hashlen = TLS13_SUITES[cipher_suite][2]
     return hkdf_expand_label(secrets, b"traffic upd", b"", hashlen, hashlen, stream=stream)
+
+
+# ---- the TLS 1.3 key schedule above the traffic secrets -----------------------
+def tls13_suite(cipher_suite):
+    """The ``TLS13_SUITES`` row of a suite id; ValueError for an id that is not in the table."""
+    try:
+        return TLS13_SUITES[cipher_suite]
+    except (KeyError, TypeError):
+        raise ValueError("cipher suite %r is not in TLS13_SUITES" % (cipher_suite,))
+
+
+def _hash_rows(t, hashlen, what, n=None):
+    """The row count of ``t``, a tensor of ``hashlen``-byte rows (of ``n`` rows when given)."""
+    if t.numel() % hashlen or (n is not None and t.numel() != n * hashlen):
+        raise ValueError("%s must hold one %d-byte row per session" % (what, hashlen))
+    return t.numel() // hashlen
+
+
+def _out_rows(out, n, width, like, stream):
+    """``out``, or a new n x width tensor that belongs to ``stream``'s allocations."""
+    if out is None:
+        torch = _torch()
+        with torch.cuda.stream(torch_stream(stream)):
+            return torch.empty((n, width), dtype=torch.uint8, device=like.device)
+    if out.numel() != n * width:
+        raise ValueError("out must hold %d bytes per session" % width)
+    return out
+
+
+def hkdf_extract(salts, ikm, hashlen, out=None, stream=None):
+    """``secureHMAC(salt_i, ikm_i)`` (cryptomath.py:128-132), HKDF-Extract, for
+    every session (tg_hkdf_extract).  ``salts``: n x hashlen device bytes, or
+    ``None`` for ``hashlen`` zero bytes; ``ikm``: n x (1..1024) device bytes, or
+    ``None`` for ``hashlen`` zero bytes.  One of the two, or ``out``, gives n.
+    Returns / fills ``out`` (n x hashlen)."""
+    if ikm is not None and ikm.ndim != 2:
+        raise ValueError("ikm must be a 2-D tensor, one row per session")
+    given = ikm if ikm is not None else salts if salts is not None else out
+    if given is None:
+        raise ValueError("salts, ikm and out are all None: the row count is unknown")
+    n = ikm.shape[0] if ikm is not None else _hash_rows(given, hashlen, "salts")
+    if salts is not None:
+        _hash_rows(salts, hashlen, "salts", n)
+    out = _out_rows(out, n, hashlen, given, stream)
+    _lib.check(_lib.load().tg_hkdf_extract(hashlen, _ptr(salts, "salts"), _ptr(ikm, "ikm"),
+                                           ikm.shape[1] if ikm is not None else 0, n, _ptr(out, "out"),
+                                           _stream(stream)))
+    return out
+
+
+def hkdf_expand_label_rows(secrets, label, contexts, length, hashlen, out=None, stream=None):
+    """``HKDF_expand_label(secret_i, label, context_i, length)`` (cryptomath.py:155-173)
+    for every row of ``secrets`` (n x hashlen device bytes) with its own row
+    of ``contexts`` (n x 0..64 device bytes; ``None`` = no context)
+    (tg_hkdf_expand_label_rows).  ``label`` is host bytes shared by all rows,
+    without "tls13 ".  Returns / fills ``out`` (n x length, at most a digest)."""
+    n = _hash_rows(secrets, hashlen, "secrets")
+    ctxlen = 0
+    if contexts is not None:
+        if contexts.ndim != 2 or contexts.shape[0] != n:
+            raise ValueError("contexts must have one row per secret")
+        ctxlen = contexts.shape[1]
+    out = _out_rows(out, n, length, secrets, stream)
+    label = bytes(label)
+    _lib.check(_lib.load().tg_hkdf_expand_label_rows(hashlen, _ptr(secrets, "secrets"), n, label or None,
+                                                     len(label), _ptr(contexts, "contexts") if ctxlen else None,
+                                                     ctxlen, length, _ptr(out, "out"), _stream(stream)))
+    return out
+
+
+def derive_secret(secrets, label, hashes, hashlen, out=None, stream=None):
+    """``derive_secret(secret_i, label, transcript_i)`` (cryptomath.py:175-195):
+    ``hashes`` holds every session's transcript hash (n x hashlen device bytes);
+    ``None`` is the reference's ``handshake_hashes=None``, the hash of the empty
+    transcript.  Returns / fills ``out`` (n x hashlen)."""
+    n = _hash_rows(secrets, hashlen, "secrets")
+    out = _out_rows(out, n, hashlen, secrets, stream)
+    label = bytes(label)
+    if hashes is not None:
+        _hash_rows(hashes, hashlen, "hashes", n)
+    _lib.check(_lib.load().tg_hkdf_expand_label_rows(hashlen, _ptr(secrets, "secrets"), n, label or None,
+                                                     len(label), _ptr(hashes, "hashes"), hashlen, hashlen,
+                                                     _ptr(out, "out"), _stream(stream)))
+    return out
+
+
+def tls13_finished(secrets, hashes, hashlen, out=None, stream=None):
+    """The Finished verify_data of every session (tlsconnection.py:3203-3207):
+    ``secureHMAC(HKDF_expand_label(secret_i, "finished", "", hashlen), hash_i)``
+    with ``secrets`` the handshake traffic secrets (or binder keys) and
+    ``hashes`` the transcript hashes, n x hashlen device bytes each
+    (tg_tls13_finished).  Returns / fills ``out`` (n x hashlen)."""
+    n = _hash_rows(secrets, hashlen, "secrets")
+    _hash_rows(hashes, hashlen, "hashes", n)
+    out = _out_rows(out, n, hashlen, secrets, stream)
+    _lib.check(_lib.load().tg_tls13_finished(hashlen, _ptr(secrets, "secrets"), _ptr(hashes, "hashes"), n,
+                                             _ptr(out, "out"), _stream(stream)))
+    return out
+
+
+def tls13_handshake_secrets(cipher_suite, shared, hello_hash, psk=None, stream=None):
+    """The handshake stage of the schedule (tlsconnection.py:3036-3050) for
+    many sessions in one launch (tg_tls13_handshake_secrets): ``shared`` is
+    every session's (EC)DHE shared secret (n x 1..1024 device bytes),
+    ``hello_hash`` the transcript hash through ServerHello and ``psk`` the
+    PSK (n x hashlen each; ``psk=None``: no PSK).  Returns ``(handshake_secret,
+    client_hs, server_hs)``, n x hashlen each; the early secret and "derived"
+    stay in registers."""
+    torch = _torch()
+    hashlen = tls13_suite(cipher_suite)[2]
+    if shared.ndim != 2:
+        raise ValueError("shared must be a 2-D tensor, one row per session")
+    n = shared.shape[0]
+    _hash_rows(hello_hash, hashlen, "hello_hash", n)
+    if psk is not None:
+        _hash_rows(psk, hashlen, "psk", n)
+    with torch.cuda.stream(torch_stream(stream)):
+        out = torch.empty((3, n, hashlen), dtype=torch.uint8, device=shared.device)
+    _lib.check(_lib.load().tg_tls13_handshake_secrets(hashlen, _ptr(psk, "psk"), _ptr(shared, "shared"),
+                                                      shared.shape[1], _ptr(hello_hash, "hello_hash"), n,
+                                                      _ptr(out[0], "out"), _ptr(out[1], "out"), _ptr(out[2], "out"),
+                                                      _stream(stream)))
+    return out[0], out[1], out[2]
+
+
+def tls13_application_secrets(cipher_suite, handshake_secrets, finished_hash, in_place=False, stream=None):
+    """The application stage (tlsconnection.py:3218-3224, :3326) for many
+    sessions in one launch (tg_tls13_application_secrets): from the handshake
+    secrets and the transcript hash through the server's Finished (n x hashlen
+    device bytes each) to ``(master, client_ap, server_ap, exporter_master)``.
+    ``in_place``: the master secrets overwrite ``handshake_secrets``, which is
+    returned as ``master``."""
+    torch = _torch()
+    hashlen = tls13_suite(cipher_suite)[2]
+    n = _hash_rows(handshake_secrets, hashlen, "handshake_secrets")
+    _hash_rows(finished_hash, hashlen, "finished_hash", n)
+    with torch.cuda.stream(torch_stream(stream)):
+        out = torch.empty((4, n, hashlen), dtype=torch.uint8, device=handshake_secrets.device)
+    master = handshake_secrets if in_place else out[0]
+    _lib.check(_lib.load().tg_tls13_application_secrets(hashlen, _ptr(handshake_secrets, "handshake_secrets"),
+                                                        _ptr(finished_hash, "finished_hash"), n,
+                                                        _ptr(master, "master"), _ptr(out[1], "out"),
+                                                        _ptr(out[2], "out"), _ptr(out[3], "out"), _stream(stream)))
+    return master, out[1], out[2], out[3]
+
+
+def tls13_binders(psk, hashes, hashlen, external, stream=None):
+    """The PSK binder of every row (``HandshakeHelpers._calc_binder``,
+    handshakehelpers.py:44-61): ``psk`` n x (1..1024) device bytes, ``hashes``
+    the transcript hash that includes the truncated ClientHello (n x hashlen);
+    ``external`` picks "ext binder" (an out-of-band PSK) or "res binder" (a
+    ticket's).  Extract, Derive-Secret over the empty transcript and Finished,
+    three launches on ``stream``; returns n x hashlen device bytes."""
+    early = hkdf_extract(None, psk, hashlen, stream=stream)
+    key = derive_secret(early, b"ext binder" if external else b"res binder", None, hashlen, stream=stream)
+    return tls13_finished(key, hashes, hashlen, stream=stream)
+
+
+def tls13_resumption_psk(res_master, nonces, hashlen, stream=None):
+    """The PSK of a session ticket (``calc_res_binder_psk``,
+    handshakehelpers.py:64-72): ``HKDF_expand_label(res_master_i, "resumption",
+    ticket_nonce_i, hashlen)`` with one nonce per row (n x 0..64 device bytes)."""
+    return hkdf_expand_label_rows(res_master, b"resumption", nonces, hashlen, hashlen, stream=stream)

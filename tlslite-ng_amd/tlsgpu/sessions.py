@@ -160,6 +160,45 @@ class Sessions(object):
             raise ValueError("secrets must hold one %d-byte row per slot" % self.hashlen)
         self._rekey(_lib.TG_REKEY_INSTALL, slots, secrets, n, stream)
 
+    def _need_tls13_suite(self):
+        self._need_tls13()
+        if self.cipher_suite not in keysetup.TLS13_SUITES:
+            raise ValueError("the TLS 1.3 key schedule needs Sessions with their TLS 1.3 cipher_suite")
+
+    def install_handshake(self, slots, shared, hello_hash, side, psk=None, stream=None):
+        """New TLS 1.3 connections take the sessions ``slots`` with their
+        HANDSHAKE traffic keys: row j of ``shared`` ((EC)DHE shared secrets, n
+        x 1..1024 device bytes), ``hello_hash`` (the transcript hash through
+        ServerHello) and ``psk`` (optional), n x hash length each, belongs to
+        ``slots[j]``.  The handshake stage of the schedule
+        (``keysetup.tls13_handshake_secrets``, tlsconnection.py:3036-3050) and
+        then ``install`` of the traffic secrets of ``side`` ("client" / "server"
+        write keys, as ``keysetup.tls12_side`` takes it) on the same stream:
+        table entry, IV row, secret row, counter 0.  Returns the handshake
+        secrets (n x hash length), for ``install_application``."""
+        self._need_tls13_suite()
+        side = keysetup.tls12_side(side)
+        hs, client, server = keysetup.tls13_handshake_secrets(self.cipher_suite, shared, hello_hash, psk=psk,
+                                                              stream=stream)
+        self.install(slots, server if side == keysetup.SERVER_WRITE else client, stream=stream)
+        return hs
+
+    def install_application(self, slots, handshake_secrets, finished_hash, side, stream=None):
+        """The sessions ``slots`` move on to their APPLICATION traffic keys:
+        the application stage (``keysetup.tls13_application_secrets``,
+        tlsconnection.py:3218-3224) from row j of ``handshake_secrets`` and of
+        ``finished_hash`` (the transcript hash through the server's Finished),
+        then ``install`` of the traffic secrets of ``side`` on the same stream.
+        Returns the master secrets (n x hash length): "res master" is
+        ``keysetup.derive_secret`` of them once the client's Finished is in
+        the transcript."""
+        self._need_tls13_suite()
+        side = keysetup.tls12_side(side)
+        master, client, server, _ = keysetup.tls13_application_secrets(self.cipher_suite, handshake_secrets,
+                                                                       finished_hash, stream=stream)
+        self.install(slots, server if side == keysetup.SERVER_WRITE else client, stream=stream)
+        return master
+
     def seal(self, session, n, data, data_off, data_len, ctype, wire, wire_off, wire_len,
              pad_len=None, seq_out=None, stream=None):
         records.seal_session_records(self.table, self.version, self.ivs, session, n, data, data_off,
