@@ -21,9 +21,10 @@
 //                    KeyUpdate), fused: HKDF, key expansion, H and the
 //                    entry's store in one lane (tg_key_replace_device,
 //                    tg_sessions_rekey).
-// The AES schedule, the entry store, the word helpers and HKDF's T(1) (load_be,
-// hkdf_t1) are keysetup_dev.h's, shared with the TLS 1.2 key setup of tls12.hip
-// and the TLS 1.3 key schedule of tls13.hip.
+// The AES schedule, the entry store, the word helpers, the key loads, the
+// digest stores and HKDF's T(1) (hkdf_t1, on the one HMAC core) are
+// keysetup_dev.h's, shared with the TLS 1.0 - 1.2 key setup of tls12.hip and
+// tls10.hip and the TLS 1.3 key schedule of tls13.hip.
 #include "keysetup_dev.h"
 
 namespace tg {
@@ -32,21 +33,12 @@ namespace {
 template <class H>
 __global__ __launch_bounds__(256) void hkdf_kernel(tg::HkdfMsg msg, const uint8_t* __restrict__ secrets, uint64_t n,
                             uint8_t* __restrict__ out) {
-    using W = typename H::word;
-    constexpr int WB = sizeof(W);
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint8_t* sec = secrets + (uint64_t)H::kHash * i;
-    W key[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) key[k] = k * WB < H::kHash ? load_be<H>(sec + k * WB) : W(0);
-    W st[8];
+    typename H::word key[16], st[8];
+    key_from_row<H, H::kHash>(secrets + (uint64_t)H::kHash * i, key);
     hkdf_t1<H>(msg, key, st);
-    uint8_t* o = out + (uint64_t)msg.outlen * i;
-    for (uint32_t k = 0; k < msg.outlen; ++k) {
-        const W wv = st[k / WB];
-        o[k] = (uint8_t)(wv >> (8 * (WB - 1 - (k % WB))));
-    }
+    store_digest_bytes<H>(st, out + (uint64_t)msg.outlen * i, msg.outlen);
 }
 
 template <int NK, int LAYOUT>
@@ -104,35 +96,19 @@ __global__ __launch_bounds__(256) void rekey_kernel(RekeyMsgs msgs, const uint32
         for (int k = 0; k < KW; ++k) rk[k] = load_u32u(src + 4 * KW * j + 4 * k);
     } else {
         using W = typename H::word;
-        constexpr int WB = sizeof(W), HW = H::kHash / 4;   // secret as 32-bit words
         const uint8_t* from = src ? src + (uint64_t)H::kHash * j : secrets + (uint64_t)H::kHash * s;
         W sec[16], st[8];
         uint32_t d[12];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (k * WB >= H::kHash) {
-                sec[k] = W(0);
-            } else if constexpr (WB == 4) {
-                sec[k] = bswap32(load_u32u(from + 4 * k));
-            } else {
-                sec[k] = ((uint64_t)bswap32(load_u32u(from + 8 * k)) << 32) | bswap32(load_u32u(from + 8 * k + 4));
-            }
-        }
+        key_from_row<H, H::kHash>(from, sec);
         if (!src) {   // KeyUpdate: the secret advances (uniform branch)
             hkdf_t1<H>(msgs.upd, sec, st);
 #pragma unroll
             for (int k = 0; k < H::kStateOut; ++k) sec[k] = st[k];
         }
-        if (secrets) {
-            uint8_t* to = secrets + (uint64_t)H::kHash * s;
-            digest_words<H>(sec, d);
-#pragma unroll
-            for (int k = 0; k < HW; ++k) store_u32u(to + 4 * k, bswap32(d[k]));
-        }
+        if (secrets) store_digest<H>(sec, secrets + (uint64_t)H::kHash * s);
         hkdf_t1<H>(msgs.iv, sec, st);
         digest_words<H>(st, d);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) store_u32u(iv_table + 12 * s + 4 * k, bswap32(d[k]));
+        store_words<3>(d, iv_table + 12 * s);
         hkdf_t1<H>(msgs.key, sec, st);
         digest_words<H>(st, d);
 #pragma unroll

@@ -1,9 +1,12 @@
-// prf_dev.h -- what the TLS key-derivation translation units share (tls12.hip:
-// the TLS 1.2 PRF and its installs; tls10.hip: the TLS 1.0 / 1.1 PRF and its
-// install): HMAC with the key as two midstates, the HMAC of a packed message
-// template, P_hash into a register window, the CBC table row, and the launch
-// and argument checks both files make.  Anonymous namespace, as keysetup_dev.h:
-// each translation unit has its own copy.
+// prf_dev.h -- what the TLS 1.0 - 1.2 key-derivation translation units share
+// (tls12.hip: the TLS 1.2 PRF and its installs; tls10.hip: the TLS 1.0 / 1.1 PRF
+// and its install; tls13.hip takes the launch helpers): the HMAC of a packed
+// message template, P_hash into a register window, the slices of a key block,
+// the CBC table row, the template packer (one word's text for both pack
+// kernels, and the host's scratch / pack / launch / release sequence) and the
+// argument checks the entry points share.  The HMAC core and the key loads are
+// keysetup_dev.h's.  Anonymous namespace, as there: each translation unit has
+// its own copy.
 //
 // Byte order.  A hash H says with H::kBigEndian how its message words, its bit
 // length and its digest are laid out (sha.h: big-endian, the length in the
@@ -19,65 +22,7 @@
 namespace tg {
 namespace {
 
-// ---- HMAC with the key as midstates ----------------------------------------
-template <class H>
-struct Hm {
-    typename H::word in[8], out[8];
-};
-
-// key: the HMAC key as words of H, zero-padded to one hash block.
-template <class H>
-__device__ __forceinline__ void hm_key(const typename H::word key[16], Hm<H>& h) {
-    using W = typename H::word;
-    const W ipad = (W)0x3636363636363636ull, opad = (W)0x5c5c5c5c5c5c5c5cull;
-    W blk[16];
-    H::init(h.in);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ ipad;
-    H::compress(h.in, blk);
-    H::init(h.out);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = key[k] ^ opad;
-    H::compress(h.out, blk);
-}
-
-// One digest as the whole message behind a key block: its padded block.
-template <class H>
-__device__ __forceinline__ void digest_block(const typename H::word d[8], typename H::word blk[16]) {
-    using W = typename H::word;
-    constexpr int dw = H::kStateOut;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) blk[k] = k < dw ? d[k] : W(0);
-    if constexpr (H::kBigEndian) {
-        blk[dw] = (W)1 << (8 * sizeof(W) - 1);                  // 0x80 terminator
-        blk[15] = (W)((H::kBlock + H::kHash) * 8);              // bit length of block + digest
-    } else {
-        blk[dw] = (W)0x80;
-        blk[14] = (W)((H::kBlock + H::kHash) * 8);              // its low word; word 15 stays 0
-    }
-}
-
-// st: the inner digest on entry, the HMAC on return.
-template <class H>
-__device__ __forceinline__ void hm_outer(const Hm<H>& h, typename H::word st[8]) {
-    typename H::word blk[16];
-    digest_block<H>(st, blk);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = h.out[k];
-    H::compress(st, blk);
-}
-
-// st = HMAC(a), a one digest: A(i + 1) from A(i).
-template <class H>
-__device__ __forceinline__ void hm_digest(const Hm<H>& h, const typename H::word a[8], typename H::word st[8]) {
-    typename H::word blk[16];
-    digest_block<H>(a, blk);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) st[k] = h.in[k];
-    H::compress(st, blk);
-    hm_outer<H>(h, st);
-}
-
+// ---- HMAC over a packed template (Hm, hm_key, hm_outer: keysetup_dev.h) ------
 // st = HMAC over a packed template of nb blocks (t: its word 0 for this lane,
 // words n apart, in H's byte order).  SPLICE: the digest a replaces the hole at
 // its front.
@@ -116,9 +61,6 @@ __device__ __forceinline__ void hm_tmpl(const Hm<H>& h, const uint32_t* __restri
 // t2: this lane's word 0 of the templates of A(0) and of A(i) || A(0).
 // The window moves down one digest per block (compile-time indices inside a
 // loop that is not unrolled); after NB rounds digest 0 is at kb[0].
-// (key_block of tls12.hip is this loop with the master secret's load in front;
-// it keeps its own text so that the TLS 1.2 kernels stay instruction for
-// instruction what they were.)
 template <class H, int NB>
 __device__ __forceinline__ void p_hash_words(const Hm<H>& h, const uint32_t* __restrict__ t1, uint32_t nb1,
                                              const uint32_t* __restrict__ t2, uint32_t nb2, uint64_t n,
@@ -150,6 +92,33 @@ __device__ __forceinline__ void p_hash_words(const Hm<H>& h, const uint32_t* __r
 #pragma unroll
             for (int k = 0; k < 8; ++k) a[k] = o[k];
         }
+    }
+}
+
+// ---- slices of the key block ---------------------------------------------------
+// The key block holds a client's N words at kb[at] and the server's N behind
+// them; out gets this side's.  Both sides' words are read as values and one is
+// selected: a select of two addresses inside kb would keep the window in memory.
+template <int N>
+__device__ __forceinline__ void side_words(const uint32_t* kb, int at, bool server, uint32_t* out) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const uint32_t c = kb[at + k], sv = kb[at + N + k];
+        out[k] = server ? sv : c;
+    }
+}
+
+// A MAC key of HM's digest length, big-endian 32-bit words, as words of HM
+// zero-padded to one block (store_cbc_row's m).
+template <class HM>
+__device__ __forceinline__ void mac_words(const uint32_t mk[HM::kHash / 4], typename HM::word m[16]) {
+    constexpr int MW = HM::kHash / 4;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = 0;
+#pragma unroll
+    for (int k = 0; k < MW; ++k) {
+        if constexpr (sizeof(typename HM::word) == 4) m[k] = mk[k];
+        else if (k % 2 == 0) m[k / 2] = ((uint64_t)mk[k] << 32) | mk[k + 1];
     }
 }
 
@@ -201,13 +170,116 @@ __device__ __forceinline__ void store_cbc_row(const uint8_t* sb, uint32_t rk[60]
     o->pad[1] = 0;
 }
 
-// ---- launches and the checks of a tg_tls12_install ------------------------------
+// ---- launches ---------------------------------------------------------------------
 inline bool launched() { return hipGetLastError() == hipSuccess; }
 
 inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 constexpr uint64_t kMaxSessions = 1ull << 31;   // grids of every kernel stay below 2^31 blocks
 
+// ---- message templates ----------------------------------------------------------
+// What every template of a launch shares: label and seed (public handshake
+// values) and where the words go, word w of session i at tmpl[w * n + i].  How
+// many templates there are and how long each is is the file's own geometry
+// (PrfGeom of tls12.hip, Tls10Geom of tls10.hip).
+struct Pack {
+    uint32_t label[8];      // LE words of the label's bytes
+    uint32_t labellen;
+    uint32_t len0, len1;    // the seed is row i of seed0 then row i of seed1
+    const uint8_t* seed0;
+    const uint8_t* seed1;
+    uint64_t n;
+    uint32_t* tmpl;
+    uint32_t words;         // of all templates of one session
+};
+
+// Word wi of session i's template of ``words`` words: a hole of ``hole`` bytes
+// (A(i)'s place), label, seed, 0x80, zeros and the bit length behind a key
+// block of ``block`` bytes.  le: MD5's order (little-endian words, the length's
+// low word last but one); else SHA's (big-endian, the length in the last word).
+__device__ __forceinline__ uint32_t pack_word(const Pack& p, uint64_t i, uint32_t wi, uint32_t hole, uint32_t words,
+                                              uint32_t block, bool le) {
+    const uint32_t s0 = hole + p.labellen, s1 = s0 + p.len0, end = s1 + p.len1;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; ++b) {
+        const uint32_t at = 4 * wi + b;
+        uint32_t byte = 0;
+        if (at < hole) {
+            byte = 0;
+        } else if (at < s0) {
+            const uint32_t idx = at - hole;
+            uint32_t lw = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) lw = (idx >> 2) == k ? p.label[k] : lw;
+            byte = (lw >> (8 * (idx & 3))) & 0xffu;
+        } else if (at < s1) {
+            byte = ((gptr_c)p.seed0)[(uint64_t)p.len0 * i + (at - s0)];
+        } else if (at < end) {
+            byte = ((gptr_c)p.seed1)[(uint64_t)p.len1 * i + (at - s1)];
+        } else if (at == end) {
+            byte = 0x80;
+        }
+        v |= byte << (le ? 8 * b : 24 - 8 * b);
+    }
+    // the bit length, key block included: below 2^32, the words above it stay 0
+    if (wi == (le ? words - 2 : words - 1)) v = (block + end) * 8u;
+    return v;
+}
+
+// Packs the templates of n sessions into scratch taken from sc: ``words`` words
+// a session, laid out by ``kernel`` (the file's own pack kernel) under geometry g.
+template <class G>
+int pack_templates(void (*kernel)(Pack, G), const G& g, const uint8_t* label, size_t labellen, const uint8_t* seed0,
+                   size_t len0, const uint8_t* seed1, size_t len1, uint64_t n, Scratch& sc, Pack* p, hipStream_t s) {
+    *p = Pack{};
+    for (size_t k = 0; k < labellen; ++k) p->label[k >> 2] |= (uint32_t)label[k] << (8 * (k & 3));
+    p->labellen = (uint32_t)labellen;
+    p->seed0 = seed0;
+    p->len0 = (uint32_t)len0;
+    p->seed1 = seed1;
+    p->len1 = (uint32_t)len1;
+    p->n = n;
+    p->words = g.words();
+    const size_t bytes = (size_t)p->words * 4 * n;
+    if (int rc = sc.alloc(bytes)) return rc;
+    p->tmpl = sc.take<uint32_t>(bytes, 256);
+    const uint64_t threads = (uint64_t)p->words * n;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, *p, g);
+    return launched() ? TG_OK : TG_EHIP;
+}
+
+// One derivation over templates: scratch, the pack launch, ``launch(tmpl)`` (0
+// or a TG_ code) and the scratch's release behind it.  packmsg / launchmsg: the
+// error text when the first / the second fails.
+template <class G, class F>
+int with_templates(void (*kernel)(Pack, G), const G& g, const uint8_t* label, size_t labellen, const uint8_t* seed0,
+                   size_t len0, const uint8_t* seed1, size_t len1, uint64_t n, hipStream_t s, const char* packmsg,
+                   const char* launchmsg, F launch) {
+    Scratch sc(s);
+    Pack p;
+    int rc = pack_templates(kernel, g, label, labellen, seed0, len0, seed1, len1, n, sc, &p, s);
+    if (rc) return fail(rc, "%s", packmsg);
+    rc = launch(p.tmpl);
+    if (rc) return fail(rc, "%s", launchmsg);
+    rc = sc.release();
+    return rc ? fail(rc, "scratch release failed") : TG_OK;
+}
+
+// The argument errors tg_tls12_prf and tg_tls10_prf share, in their order.
+inline int prf_args_error(size_t secretlen, size_t maxsecret, size_t labellen, const uint8_t* label, size_t seedlen,
+                          size_t outlen, uint64_t n) {
+    if (secretlen == 0 || secretlen > maxsecret)
+        return fail(TG_EINVAL, "secret length must be 1..%zu, got %zu", maxsecret, secretlen);
+    if (labellen > 32) return fail(TG_EINVAL, "label length must be at most 32, got %zu", labellen);
+    if (seedlen > 128) return fail(TG_EINVAL, "seed length must be at most 128, got %zu", seedlen);
+    if (outlen == 0 || outlen > 256) return fail(TG_EINVAL, "output length must be 1..256, got %zu", outlen);
+    if (labellen && !label) return fail(TG_EINVAL, "null label");
+    if (n > kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
+    return TG_OK;
+}
+
+// ---- the checks of a tg_tls12_install -------------------------------------------
 const uint8_t kKeyExpansion[] = "key expansion";
 
 // The struct's own errors, whatever the key is (tg_sessions_rekey's order).

@@ -12,7 +12,8 @@
 //     the key block PRF(master secret, "key expansion", server_random ||
 //     client_random) cut as client MAC, server MAC, client key, server key.
 //
-// This is the design of tls12.hip with one addition.  tls10_pack_kernel lays
+// This is the design of tls12.hip with one addition (the shared text is
+// prf_dev.h's and keysetup_dev.h's, as there).  tls10_pack_kernel lays
 // the public messages out once in library scratch, word w of session i at
 // tmpl[w * n + i]: A(0) and A(i) || A(0), each padded once for MD5
 // (little-endian words, the length in word 14, a 16-byte hole for A(i)) and
@@ -60,57 +61,19 @@ Tls10Geom tls10_geom(size_t msglen) {
     return g;
 }
 
-struct Tls10Pack {
-    uint32_t label[8];      // LE words of the label's bytes
-    uint32_t labellen;
-    uint32_t len0, len1;    // the seed is row i of seed0 then row i of seed1
-    const uint8_t* seed0;
-    const uint8_t* seed1;
-    Tls10Geom g;
-    uint64_t n;
-    uint32_t* tmpl;
-};
-
-__global__ __launch_bounds__(256) void tls10_pack_kernel(Tls10Pack p) {
+__global__ __launch_bounds__(256) void tls10_pack_kernel(Pack p, Tls10Geom g) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t wt = p.g.words();
-    if (gid >= p.n * wt) return;
+    if (gid >= p.n * p.words) return;
     const uint64_t i = gid % p.n;
     const uint32_t w = (uint32_t)(gid / p.n);
     // which of the four templates, and the word's place in it
-    const uint32_t e0 = 16 * p.g.nb1, e1 = e0 + 16 * p.g.nbm2, e2 = e1 + 16 * p.g.nb1;
+    const uint32_t e0 = 16 * g.nb1, e1 = e0 + 16 * g.nbm2, e2 = e1 + 16 * g.nb1;
     const bool le = w < e1;                         // the MD5 pair comes first
     const bool second = le ? w >= e0 : w >= e2;     // A(i) || A(0)
     const uint32_t base = w < e0 ? 0u : w < e1 ? e0 : w < e2 ? e1 : e2;
-    const uint32_t words = w < e0 ? e0 : w < e1 ? e1 - e0 : w < e2 ? e2 - e1 : wt - e2;
-    const uint32_t wi = w - base;
+    const uint32_t words = w < e0 ? e0 : w < e1 ? e1 - e0 : w < e2 ? e2 - e1 : p.words - e2;
     const uint32_t hole = second ? (le ? (uint32_t)Md5::kHash : (uint32_t)Sha1::kHash) : 0u;
-    const uint32_t s0 = hole + p.labellen, s1 = s0 + p.len0, end = s1 + p.len1;
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b) {
-        const uint32_t at = 4 * wi + b;
-        uint32_t byte = 0;
-        if (at < hole) {
-            byte = 0;
-        } else if (at < s0) {
-            const uint32_t idx = at - hole;
-            uint32_t lw = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) lw = (idx >> 2) == k ? p.label[k] : lw;
-            byte = (lw >> (8 * (idx & 3))) & 0xffu;
-        } else if (at < s1) {
-            byte = ((gptr_c)p.seed0)[(uint64_t)p.len0 * i + (at - s0)];
-        } else if (at < end) {
-            byte = ((gptr_c)p.seed1)[(uint64_t)p.len1 * i + (at - s1)];
-        } else if (at == end) {
-            byte = 0x80;
-        }
-        v |= byte << (le ? 8 * b : 24 - 8 * b);
-    }
-    // the bit length, key block included: below 2^32, its high word stays 0
-    if (wi == (le ? words - 2 : words - 1)) v = (64u + end) * 8u;
-    p.tmpl[(uint64_t)w * p.n + i] = v;
+    p.tmpl[(uint64_t)w * p.n + i] = pack_word(p, i, w - base, hole, words, 64u, le);
 }
 
 // This lane's word 0 of each template.
@@ -133,37 +96,15 @@ __global__ __launch_bounds__(256) void tls10_prf_kernel(const uint32_t* __restri
                                                         uint64_t n, uint32_t outlen, uint8_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const gptr_c sec = (gptr_c)(secrets + (uint64_t)secretlen * i);
+    const uint8_t* sec = secrets + (uint64_t)secretlen * i;
     const uint32_t half = (secretlen + 1) / 2, at2 = secretlen - half;   // S1 = [0, half), S2 = [at2, L)
     Hm<Md5> hm;
     Hm<Sha1> hs;
     {
         uint32_t key[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t at = (uint32_t)(4 * k + b);
-                uint32_t byte = 0;
-                if (at < half) byte = sec[at];
-                v |= byte << (8 * b);
-            }
-            key[k] = v;
-        }
+        key_from_bytes<Md5>(sec, half, key);
         hm_key<Md5>(key, hm);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t at = (uint32_t)(4 * k + b);
-                uint32_t byte = 0;
-                if (at < half) byte = sec[at2 + at];
-                v = (v << 8) | byte;
-            }
-            key[k] = v;
-        }
+        key_from_bytes<Sha1>(sec + at2, half, key);
         hm_key<Sha1>(key, hs);
     }
     const Tls10Tmpl t = tls10_tmpl(tmpl, g, n, i);
@@ -246,17 +187,15 @@ __global__ __launch_bounds__(256) void tls11_cbcrow_install_kernel(const uint32_
     const Tls10Tmpl t = tls10_tmpl(tmpl, g, n, j);
     uint32_t kb[NBM * 4];   // big-endian words of the key block's bytes
     {
-        uint32_t key[16];   // S1: the master secret's first 24 bytes, LE words
-#pragma unroll
-        for (int k = 0; k < 16; ++k) key[k] = k < 6 ? load_u32u(ms + 48 * j + 4 * k) : 0u;
+        uint32_t key[16];   // S1: the master secret's first 24 bytes
+        key_from_row<Md5, 24>(ms + 48 * j, key);
         Hm<Md5> h;
         hm_key<Md5>(key, h);
         p_hash_words<Md5, NBM>(h, t.m1, g.nb1, t.m2, g.nbm2, n, kb);
     }
     {
-        uint32_t key[16];   // S2: its last 24 bytes, big-endian words
-#pragma unroll
-        for (int k = 0; k < 16; ++k) key[k] = k < 6 ? bswap32(load_u32u(ms + 48 * j + 24 + 4 * k)) : 0u;
+        uint32_t key[16];   // S2: its last 24 bytes
+        key_from_row<Sha1, 24>(ms + 48 * j + 24, key);
         Hm<Sha1> h;
         hm_key<Sha1>(key, h);
         uint32_t ks[NBS * 5];
@@ -265,45 +204,14 @@ __global__ __launch_bounds__(256) void tls11_cbcrow_install_kernel(const uint32_
         for (int k = 0; k < NEED; ++k) kb[k] ^= ks[k];
     }
     const bool server = side != 0;
-    uint32_t m[16];   // the MAC key, big-endian words, zero-padded
+    uint32_t mk[MW], m[16], rk[60];
+    side_words<MW>(kb, 0, server, mk);
+    mac_words<Sha1>(mk, m);
+    side_words<NK>(kb, 2 * MW, server, rk);
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k < MW) {   // both sides' words as values, then the select
-            const uint32_t c = kb[k], sv = kb[MW + k];
-            m[k] = server ? sv : c;
-        } else {
-            m[k] = 0u;
-        }
-    }
-    uint32_t rk[60];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const uint32_t c = kb[2 * MW + k], sv = kb[2 * MW + NK + k];
-        rk[k] = bswap32(server ? sv : c);
-    }
+    for (int k = 0; k < NK; ++k) rk[k] = bswap32(rk[k]);
     if (seq_next) seq_next[s] = 0;
     store_cbc_row<NK, Sha1>(sb, rk, m, rows + s, (uint32_t)TG_MAC_SHA1);
-}
-
-// ---- launchers -------------------------------------------------------------------
-// Packs the four templates of n sessions into scratch taken from sc.
-int pack_templates(const uint8_t* label, size_t labellen, const uint8_t* seed0, size_t len0, const uint8_t* seed1,
-                   size_t len1, uint64_t n, Scratch& sc, Tls10Pack* p, hipStream_t s) {
-    *p = Tls10Pack{};
-    for (size_t k = 0; k < labellen; ++k) p->label[k >> 2] |= (uint32_t)label[k] << (8 * (k & 3));
-    p->labellen = (uint32_t)labellen;
-    p->seed0 = seed0;
-    p->len0 = (uint32_t)len0;
-    p->seed1 = seed1;
-    p->len1 = (uint32_t)len1;
-    p->g = tls10_geom(labellen + len0 + len1);
-    p->n = n;
-    const size_t bytes = (size_t)p->g.words() * 4 * n;
-    if (int rc = sc.alloc(bytes)) return rc;
-    p->tmpl = sc.take<uint32_t>(bytes, 256);
-    const uint64_t threads = (uint64_t)p->g.words() * n;
-    hipLaunchKernelGGL(tls10_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, *p);
-    return launched() ? TG_OK : TG_EHIP;
 }
 
 }  // namespace
@@ -315,25 +223,17 @@ extern "C" {
 
 int tg_tls10_prf(const uint8_t* secrets, size_t secretlen, uint64_t n, const uint8_t* label, size_t labellen,
                  const uint8_t* seeds, size_t seedlen, size_t outlen, uint8_t* out, void* stream) {
-    if (secretlen == 0 || secretlen > 128)
-        return fail(TG_EINVAL, "secret length must be 1..128, got %zu", secretlen);
-    if (labellen > 32) return fail(TG_EINVAL, "label length must be at most 32, got %zu", labellen);
-    if (seedlen > 128) return fail(TG_EINVAL, "seed length must be at most 128, got %zu", seedlen);
-    if (outlen == 0 || outlen > 256) return fail(TG_EINVAL, "output length must be 1..256, got %zu", outlen);
-    if (labellen && !label) return fail(TG_EINVAL, "null label");
-    if (n > tg::kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
+    if (int rc = tg::prf_args_error(secretlen, 128, labellen, label, seedlen, outlen, n)) return rc;
     if (n == 0) return TG_OK;
     if (!secrets || !out || (seedlen && !seeds)) return fail(TG_EINVAL, "null device buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    tg::Scratch sc(s);
-    tg::Tls10Pack p;
-    int rc = tg::pack_templates(label, labellen, seeds, seedlen, nullptr, 0, n, sc, &p, s);
-    if (rc) return fail(rc, "PRF template launch failed");
-    hipLaunchKernelGGL(tg::tls10_prf_kernel, dim3(tg::blocks_of(n)), dim3(256), 0, s, p.tmpl, p.g, secrets,
-                       (uint32_t)secretlen, n, (uint32_t)outlen, out);
-    if (!tg::launched()) return fail(TG_EHIP, "PRF launch failed");
-    rc = sc.release();
-    return rc ? fail(rc, "scratch release failed") : TG_OK;
+    const tg::Tls10Geom g = tg::tls10_geom(labellen + seedlen);
+    return tg::with_templates(tg::tls10_pack_kernel, g, label, labellen, seeds, seedlen, nullptr, 0, n, s,
+                              "PRF template launch failed", "PRF launch failed", [&](const uint32_t* tmpl) {
+                                  hipLaunchKernelGGL(tg::tls10_prf_kernel, dim3(tg::blocks_of(n)), dim3(256), 0, s,
+                                                     tmpl, g, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
+                                  return tg::launched() ? TG_OK : TG_EHIP;
+                              });
 }
 
 int tg_cbc_sessions_install_tls11(tg_cbc_key* k, const tg_tls12_install* r, void* stream) {
@@ -346,23 +246,21 @@ int tg_cbc_sessions_install_tls11(tg_cbc_key* k, const tg_tls12_install* r, void
     if (r->n == 0) return TG_OK;
     if (int rc = tg::cbc_select_device(k)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    tg::Scratch sc(s);
-    tg::Tls10Pack p;
-    int rc = tg::pack_templates(tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32, r->n, sc, &p, s);
-    if (!rc) {
-        if (k->rounds == 10)
-            hipLaunchKernelGGL(tg::tls11_cbcrow_install_kernel<4>, dim3(tg::blocks_of(r->n)), dim3(256), 0, s, p.tmpl,
-                               p.g, r->slot, r->master_secrets, r->side, r->seq_next, r->n, (uint64_t)k->nkeys,
-                               k->dev_key);
-        else
-            hipLaunchKernelGGL(tg::tls11_cbcrow_install_kernel<8>, dim3(tg::blocks_of(r->n)), dim3(256), 0, s, p.tmpl,
-                               p.g, r->slot, r->master_secrets, r->side, r->seq_next, r->n, (uint64_t)k->nkeys,
-                               k->dev_key);
-        if (!tg::launched()) rc = TG_EHIP;
-    }
-    if (rc) return fail(rc, "TLS 1.1 CBC install launch failed");
-    rc = sc.release();
-    return rc ? fail(rc, "scratch release failed") : TG_OK;
+    const tg::Tls10Geom g = tg::tls10_geom(13 + 32 + 32);
+    const char* msg = "TLS 1.1 CBC install launch failed";
+    return tg::with_templates(
+        tg::tls10_pack_kernel, g, tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32, r->n, s, msg, msg,
+        [&](const uint32_t* tmpl) {
+            if (k->rounds == 10)
+                hipLaunchKernelGGL(tg::tls11_cbcrow_install_kernel<4>, dim3(tg::blocks_of(r->n)), dim3(256), 0, s, tmpl,
+                                   g, r->slot, r->master_secrets, r->side, r->seq_next, r->n, (uint64_t)k->nkeys,
+                                   k->dev_key);
+            else
+                hipLaunchKernelGGL(tg::tls11_cbcrow_install_kernel<8>, dim3(tg::blocks_of(r->n)), dim3(256), 0, s, tmpl,
+                                   g, r->slot, r->master_secrets, r->side, r->seq_next, r->n, (uint64_t)k->nkeys,
+                                   k->dev_key);
+            return tg::launched() ? TG_OK : TG_EHIP;
+        });
 }
 
 }  // extern "C"

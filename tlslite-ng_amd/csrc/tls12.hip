@@ -32,8 +32,11 @@
 // CbcKeyDev row: forward schedule, the equivalent inverse cipher's schedule
 // (build_row of aes_cbc.hip) and the two HMAC midstates of the MAC key.
 //
-// The HMAC, template, window and row helpers are in prf_dev.h, which tls10.hip
-// (the TLS 1.0 / 1.1 PRF) shares.
+// Nothing of that is this file's own text: the HMAC core and the key loads are
+// keysetup_dev.h's, the template HMAC, P_hash into the window (p_hash_words),
+// the slice selects, the row store and the packer's word are prf_dev.h's,
+// which tls10.hip (the TLS 1.0 / 1.1 PRF) shares.  Here are the geometry of the
+// two templates, the kernels and their launches.
 #include "keys.h"
 #include "prf_dev.h"
 
@@ -58,51 +61,15 @@ PrfGeom prf_geom(int hashlen, size_t msglen) {
     return g;
 }
 
-struct PrfPack {
-    uint32_t label[8];      // LE words of the label's bytes
-    uint32_t labellen;
-    uint32_t len0, len1;    // the seed is row i of seed0 then row i of seed1
-    const uint8_t* seed0;
-    const uint8_t* seed1;
-    PrfGeom g;
-    uint64_t n;
-    uint32_t* tmpl;
-};
-
-__global__ __launch_bounds__(256) void prf_pack_kernel(PrfPack p) {
+// Word w of a session: the template of A(0), then that of A(i) || A(0).
+__global__ __launch_bounds__(256) void prf_pack_kernel(Pack p, PrfGeom g) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t w1 = p.g.nb1 * (p.g.block / 4), wt = p.g.words();
-    if (gid >= p.n * wt) return;
+    if (gid >= p.n * p.words) return;
     const uint64_t i = gid % p.n;
-    const uint32_t w = (uint32_t)(gid / p.n);
+    const uint32_t w = (uint32_t)(gid / p.n), w1 = g.nb1 * (g.block / 4);
     const bool second = w >= w1;
-    const uint32_t hole = second ? p.g.hashlen : 0u;
-    const uint32_t wi = second ? w - w1 : w, words = second ? wt - w1 : w1;
-    const uint32_t s0 = hole + p.labellen, s1 = s0 + p.len0, end = s1 + p.len1;
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b) {
-        const uint32_t at = 4 * wi + b;
-        uint32_t byte = 0;
-        if (at < hole) {
-            byte = 0;
-        } else if (at < s0) {
-            const uint32_t idx = at - hole;
-            uint32_t lw = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) lw = (idx >> 2) == k ? p.label[k] : lw;
-            byte = (lw >> (8 * (idx & 3))) & 0xffu;
-        } else if (at < s1) {
-            byte = ((gptr_c)p.seed0)[(uint64_t)p.len0 * i + (at - s0)];
-        } else if (at < end) {
-            byte = ((gptr_c)p.seed1)[(uint64_t)p.len1 * i + (at - s1)];
-        } else if (at == end) {
-            byte = 0x80;
-        }
-        v = (v << 8) | byte;
-    }
-    if (wi == words - 1) v = (p.g.block + end) * 8u;   // the bit length: below 2^32, the words above it stay 0
-    p.tmpl[(uint64_t)w * p.n + i] = v;
+    p.tmpl[(uint64_t)w * p.n + i] = pack_word(p, i, second ? w - w1 : w, second ? g.hashlen : 0u,
+                                              second ? p.words - w1 : w1, g.block, false);
 }
 
 // ---- tg_tls12_prf ------------------------------------------------------------
@@ -111,25 +78,12 @@ __global__ __launch_bounds__(256) void tls12_prf_kernel(const uint32_t* __restri
                                                         const uint8_t* __restrict__ secrets, uint32_t secretlen,
                                                         uint64_t n, uint32_t outlen, uint8_t* __restrict__ out) {
     using W = typename H::word;
-    constexpr int WB = sizeof(W);
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const gptr_c sec = (gptr_c)(secrets + (uint64_t)secretlen * i);
     Hm<H> h;
     {
         W key[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            W v = 0;
-#pragma unroll
-            for (int b = 0; b < WB; ++b) {
-                const uint32_t at = (uint32_t)(k * WB + b);
-                uint32_t byte = 0;
-                if (at < secretlen) byte = sec[at];
-                v = (W)((v << 8) | byte);
-            }
-            key[k] = v;
-        }
+        key_from_bytes<H>(secrets + (uint64_t)secretlen * i, secretlen, key);
         hm_key<H>(key, h);
     }
     const uint32_t* t1 = tmpl + i;
@@ -140,12 +94,10 @@ __global__ __launch_bounds__(256) void tls12_prf_kernel(const uint32_t* __restri
     hm_tmpl<H, false>(h, t1, n, nb1, a, o);                 // A(1)
 #pragma unroll
     for (int k = 0; k < 8; ++k) a[k] = o[k];
-    const gptr op = (gptr)(out + (uint64_t)outlen * i);
+    uint8_t* op = out + (uint64_t)outlen * i;
     for (uint32_t pos = 0; pos < outlen; pos += H::kHash) { // uniform
         hm_tmpl<H, true>(h, t2, n, nb2, a, o);
-#pragma unroll
-        for (int k = 0; k < H::kHash; ++k)
-            if (pos + k < outlen) op[pos + k] = (uint8_t)(o[k / WB] >> (8 * (WB - 1 - (k % WB))));
+        store_digest_bytes<H>(o, op + pos, outlen - pos);
         if (pos + H::kHash < outlen) {
             hm_digest<H>(h, a, o);
 #pragma unroll
@@ -161,49 +113,11 @@ template <class H, int NB>
 __device__ __forceinline__ void key_block(const uint32_t* __restrict__ tmpl, uint32_t nb1, uint32_t nb2,
                                           const uint8_t* __restrict__ ms, uint64_t n, uint64_t j,
                                           uint32_t kb[NB * (H::kHash / 4)]) {
-    using W = typename H::word;
-    constexpr int HW = H::kHash / 4;
+    typename H::word key[16];
+    key_from_row<H, 48>(ms + 48 * j, key);
     Hm<H> h;
-    {
-        W key[16];   // the 48-byte master secret
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if constexpr (sizeof(W) == 4) {
-                key[k] = k < 12 ? bswap32(load_u32u(ms + 48 * j + 4 * k)) : 0u;
-            } else {
-                key[k] = k < 6 ? ((uint64_t)bswap32(load_u32u(ms + 48 * j + 8 * k)) << 32) |
-                                     bswap32(load_u32u(ms + 48 * j + 8 * k + 4))
-                               : 0ull;
-            }
-        }
-        hm_key<H>(key, h);
-    }
-    const uint32_t* t1 = tmpl + j;
-    const uint32_t* t2 = tmpl + (uint64_t)nb1 * (H::kBlock / 4) * n + j;
-    W a[8], o[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = 0;
-#pragma unroll
-    for (int k = 0; k < NB * HW; ++k) kb[k] = 0;
-    hm_tmpl<H, false>(h, t1, n, nb1, a, o);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = o[k];
-#pragma unroll 1
-    for (int b = 0; b < NB; ++b) {
-        hm_tmpl<H, true>(h, t2, n, nb2, a, o);
-        uint32_t d[12];
-        digest_words<H>(o, d);
-        // the window moves down one digest; after NB rounds digest 0 is at kb[0]
-#pragma unroll
-        for (int k = 0; k < (NB - 1) * HW; ++k) kb[k] = kb[k + HW];
-#pragma unroll
-        for (int k = 0; k < HW; ++k) kb[(NB - 1) * HW + k] = d[k];
-        if (b + 1 < NB) {
-            hm_digest<H>(h, a, o);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) a[k] = o[k];
-        }
-    }
+    hm_key<H>(key, h);
+    p_hash_words<H, NB>(h, tmpl + j, nb1, tmpl + (uint64_t)nb1 * (H::kBlock / 4) * n + j, nb2, n, kb);
 }
 
 // ---- tg_sessions_install_tls12 -----------------------------------------------
@@ -230,16 +144,12 @@ __global__ __launch_bounds__(256) void tls12_install_kernel(const uint32_t* __re
     uint32_t kb[NB * HW];
     key_block<H, NB>(tmpl, nb1, nb2, ms, n, j, kb);
     const bool server = side != 0, iv12 = ivw == 3;
-    // both sides' words are read as values and one is selected: a select of two
-    // addresses inside kb would keep the window in memory
     uint32_t rk[60];   // rk[0 .. KW): the key as LE words of its bytes
+    side_words<KW>(kb, 0, server, rk);
 #pragma unroll
-    for (int k = 0; k < KW; ++k) {
-        const uint32_t c = kb[k], sv = kb[KW + k];
-        rk[k] = bswap32(server ? sv : c);
-    }
+    for (int k = 0; k < KW; ++k) rk[k] = bswap32(rk[k]);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3; ++k) {   // the IV as side_words picks: values first, then the selects
         const uint32_t c = kb[2 * KW + k], s4 = kb[2 * KW + 1 + k], s12 = kb[2 * KW + 3 + k];
         const uint32_t sv = iv12 ? s12 : s4;
         const uint32_t v = server ? sv : c;
@@ -265,8 +175,6 @@ __global__ __launch_bounds__(256) void cbcrows_kernel(const uint32_t* __restrict
                                                        const uint8_t* __restrict__ enc_keys,
                                                        const uint8_t* __restrict__ mac_keys, uint32_t mackeylen,
                                                        uint64_t n, uint64_t nkeys, CbcKeyDev* rows, uint32_t mac) {
-    using W = typename HM::word;
-    constexpr int WB = sizeof(W);
     __shared__ uint8_t sb[256];
     for (int k = threadIdx.x; k < 256; k += blockDim.x) sb[k] = c_sbox.s[k];
     __syncthreads();
@@ -277,20 +185,8 @@ __global__ __launch_bounds__(256) void cbcrows_kernel(const uint32_t* __restrict
     uint32_t rk[60];
 #pragma unroll
     for (int k = 0; k < NK; ++k) rk[k] = load_u32u(enc_keys + 4 * NK * j + 4 * k);
-    const gptr_c mk = (gptr_c)(mac_keys + (uint64_t)mackeylen * j);
-    W m[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        W v = 0;
-#pragma unroll
-        for (int b = 0; b < WB; ++b) {
-            const uint32_t at = (uint32_t)(k * WB + b);
-            uint32_t byte = 0;
-            if (at < mackeylen) byte = mk[at];
-            v = (W)((v << 8) | byte);
-        }
-        m[k] = v;
-    }
+    typename HM::word m[16];
+    key_from_bytes<HM>(mac_keys + (uint64_t)mackeylen * j, mackeylen, m);
     store_cbc_row<NK, HM>(sb, rk, m, rows + s, mac);
 }
 
@@ -304,7 +200,6 @@ __global__ __launch_bounds__(256) void tls12_cbcrow_install_kernel(const uint32_
                                                                 const uint8_t* __restrict__ ms, uint32_t side,
                                                                 uint64_t* __restrict__ seq_next, uint64_t n,
                                                                 uint64_t nkeys, CbcKeyDev* rows, uint32_t mac) {
-    using W = typename HM::word;
     constexpr int HW = HP::kHash / 4, MW = HM::kHash / 4;
     constexpr int NEED = 2 * MW + 2 * NK, NB = (NEED + HW - 1) / HW;
     __shared__ uint8_t sb[256];
@@ -317,62 +212,24 @@ __global__ __launch_bounds__(256) void tls12_cbcrow_install_kernel(const uint32_
     uint32_t kb[NB * HW];
     key_block<HP, NB>(tmpl, nb1, nb2, ms, n, j, kb);
     const bool server = side != 0;
-    uint32_t mk[16];   // the MAC key, big-endian 32-bit words, zero-padded
+    uint32_t mk[MW], rk[60];
+    typename HM::word m[16];
+    side_words<MW>(kb, 0, server, mk);
+    mac_words<HM>(mk, m);
+    side_words<NK>(kb, 2 * MW, server, rk);
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k < MW) {   // both sides' words as values, then the select
-            const uint32_t c = kb[k], sv = kb[MW + k];
-            mk[k] = server ? sv : c;
-        } else {
-            mk[k] = 0u;
-        }
-    }
-    uint32_t rk[60];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const uint32_t c = kb[2 * MW + k], sv = kb[2 * MW + NK + k];
-        rk[k] = bswap32(server ? sv : c);
-    }
-    W m[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if constexpr (sizeof(W) == 4) {
-            m[k] = mk[k];
-        } else {
-            m[k] = k < 8 ? ((uint64_t)mk[2 * k] << 32) | mk[2 * k + 1] : 0ull;
-        }
-    }
+    for (int k = 0; k < NK; ++k) rk[k] = bswap32(rk[k]);
     if (seq_next) seq_next[s] = 0;
     store_cbc_row<NK, HM>(sb, rk, m, rows + s, mac);
 }
 
 // ---- launchers -------------------------------------------------------------------
-// Packs both templates of n sessions into scratch taken from sc.
-int pack_templates(int hashlen, const uint8_t* label, size_t labellen, const uint8_t* seed0, size_t len0,
-                   const uint8_t* seed1, size_t len1, uint64_t n, Scratch& sc, PrfPack* p, hipStream_t s) {
-    *p = PrfPack{};
-    for (size_t k = 0; k < labellen; ++k) p->label[k >> 2] |= (uint32_t)label[k] << (8 * (k & 3));
-    p->labellen = (uint32_t)labellen;
-    p->seed0 = seed0;
-    p->len0 = (uint32_t)len0;
-    p->seed1 = seed1;
-    p->len1 = (uint32_t)len1;
-    p->g = prf_geom(hashlen, labellen + len0 + len1);
-    p->n = n;
-    const size_t bytes = (size_t)p->g.words() * 4 * n;
-    if (int rc = sc.alloc(bytes)) return rc;
-    p->tmpl = sc.take<uint32_t>(bytes, 256);
-    const uint64_t threads = (uint64_t)p->g.words() * n;
-    hipLaunchKernelGGL(prf_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, *p);
-    return launched() ? TG_OK : TG_EHIP;
-}
-
 template <class H>
-int launch_install(tg_key* k, const PrfPack& p, const tg_tls12_install& r, hipStream_t s) {
+int launch_install(tg_key* k, const uint32_t* tmpl, const PrfGeom& g, const tg_tls12_install& r, hipStream_t s) {
     const int layout = k->alg == TG_CHACHA20_POLY1305 ? 3 : is_ccm(k->alg) ? 2 : (k->nkeys > 1 ? 1 : 0);
 #define TG_INSTALL(NK, L)                                                                                   \
-    hipLaunchKernelGGL((tls12_install_kernel<H, NK, L>), dim3(blocks_of(r.n)), dim3(256), 0, s, p.tmpl,     \
-                       p.g.nb1, p.g.nb2, r.slot, r.master_secrets, r.side, r.fixed_iv_len / 4, r.iv_table,  \
+    hipLaunchKernelGGL((tls12_install_kernel<H, NK, L>), dim3(blocks_of(r.n)), dim3(256), 0, s, tmpl,       \
+                       g.nb1, g.nb2, r.slot, r.master_secrets, r.side, r.fixed_iv_len / 4, r.iv_table,      \
                        r.seq_next, r.n, (uint64_t)k->nkeys, k->dev_key)
     if constexpr (H::kHash == 48) {   // aead_pair_ok: AES-256-GCM only
         if (layout == 0) TG_INSTALL(8, 0);
@@ -412,10 +269,11 @@ bool cbc_pair_ok(uint32_t hashlen, const tg_cbc_key* k) {
 }
 
 template <class HP, int NK, class HM>
-int launch_cbc_install(tg_cbc_key* k, const PrfPack& p, const tg_tls12_install& r, hipStream_t s) {
+int launch_cbc_install(tg_cbc_key* k, const uint32_t* tmpl, const PrfGeom& g, const tg_tls12_install& r,
+                       hipStream_t s) {
 #define TG_CBC_INSTALL(HM)                                                                                    \
-    hipLaunchKernelGGL((tls12_cbcrow_install_kernel<HP, NK, HM>), dim3(blocks_of(r.n)), dim3(256), 0, s, p.tmpl, \
-                       p.g.nb1, p.g.nb2, r.slot, r.master_secrets, r.side, r.seq_next, r.n,                   \
+    hipLaunchKernelGGL((tls12_cbcrow_install_kernel<HP, NK, HM>), dim3(blocks_of(r.n)), dim3(256), 0, s, tmpl,   \
+                       g.nb1, g.nb2, r.slot, r.master_secrets, r.side, r.seq_next, r.n,                       \
                        (uint64_t)k->nkeys, k->dev_key, (uint32_t)k->mac)
     TG_CBC_INSTALL(HM);
 #undef TG_CBC_INSTALL
@@ -441,6 +299,15 @@ int cbc_rows(int rounds, int mac, const uint32_t* slot, const uint8_t* enc_keys,
                         : launch_cbc_rows<8>(mac, slot, enc_keys, mac_keys, mackeylen, n, nkeys, rows, s);
 }
 
+// The key block's templates ("key expansion" || server_random || client_random)
+// of r's sessions around ``launch(tmpl, g)``; msg: the error text of either launch.
+template <class F>
+int install_templates(const tg_tls12_install* r, hipStream_t s, const char* msg, F launch) {
+    const PrfGeom g = prf_geom((int)r->hashlen, 13 + 32 + 32);
+    return with_templates(prf_pack_kernel, g, kKeyExpansion, 13, r->server_random, 32, r->client_random, 32, r->n, s,
+                          msg, msg, [&](const uint32_t* tmpl) { return launch(tmpl, g); });
+}
+
 }  // namespace
 }  // namespace tg
 
@@ -451,30 +318,22 @@ extern "C" {
 int tg_tls12_prf(int hashlen, const uint8_t* secrets, size_t secretlen, uint64_t n, const uint8_t* label,
                  size_t labellen, const uint8_t* seeds, size_t seedlen, size_t outlen, uint8_t* out, void* stream) {
     if (hashlen != 32 && hashlen != 48) return fail(TG_EINVAL, "hash length must be 32 or 48");
-    const size_t block = hashlen == 32 ? 64 : 128;
-    if (secretlen == 0 || secretlen > block)
-        return fail(TG_EINVAL, "secret length must be 1..%zu, got %zu", block, secretlen);
-    if (labellen > 32) return fail(TG_EINVAL, "label length must be at most 32, got %zu", labellen);
-    if (seedlen > 128) return fail(TG_EINVAL, "seed length must be at most 128, got %zu", seedlen);
-    if (outlen == 0 || outlen > 256) return fail(TG_EINVAL, "output length must be 1..256, got %zu", outlen);
-    if (labellen && !label) return fail(TG_EINVAL, "null label");
-    if (n > tg::kMaxSessions) return fail(TG_EINVAL, "n must be at most 2^31");
+    if (int rc = tg::prf_args_error(secretlen, hashlen == 32 ? 64 : 128, labellen, label, seedlen, outlen, n)) return rc;
     if (n == 0) return TG_OK;
     if (!secrets || !out || (seedlen && !seeds)) return fail(TG_EINVAL, "null device buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    tg::Scratch sc(s);
-    tg::PrfPack p;
-    int rc = tg::pack_templates(hashlen, label, labellen, seeds, seedlen, nullptr, 0, n, sc, &p, s);
-    if (rc) return fail(rc, "PRF template launch failed");
-    if (hashlen == 32)
-        hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha256>, dim3(tg::blocks_of(n)), dim3(256), 0, s, p.tmpl, p.g.nb1,
-                           p.g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
-    else
-        hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha384>, dim3(tg::blocks_of(n)), dim3(256), 0, s, p.tmpl, p.g.nb1,
-                           p.g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
-    if (!tg::launched()) return fail(TG_EHIP, "PRF launch failed");
-    rc = sc.release();
-    return rc ? fail(rc, "scratch release failed") : TG_OK;
+    const tg::PrfGeom g = tg::prf_geom(hashlen, labellen + seedlen);
+    return tg::with_templates(
+        tg::prf_pack_kernel, g, label, labellen, seeds, seedlen, nullptr, 0, n, s, "PRF template launch failed",
+        "PRF launch failed", [&](const uint32_t* tmpl) {
+            if (hashlen == 32)
+                hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha256>, dim3(tg::blocks_of(n)), dim3(256), 0, s, tmpl,
+                                   g.nb1, g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
+            else
+                hipLaunchKernelGGL(tg::tls12_prf_kernel<tg::Sha384>, dim3(tg::blocks_of(n)), dim3(256), 0, s, tmpl,
+                                   g.nb1, g.nb2, secrets, (uint32_t)secretlen, n, (uint32_t)outlen, out);
+            return tg::launched() ? TG_OK : TG_EHIP;
+        });
 }
 
 int tg_cbc_key_create_device(const uint8_t* enc_keys, size_t keylen, const uint8_t* mac_keys, size_t mackeylen,
@@ -533,16 +392,11 @@ int tg_sessions_install_tls12(tg_key* k, const tg_tls12_install* r, void* stream
     if (r->n == 0) return TG_OK;
     if (int rc = tg::select_device(k)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    tg::Scratch sc(s);
-    tg::PrfPack p;
-    int rc = tg::pack_templates((int)r->hashlen, tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32,
-                                r->n, sc, &p, s);
-    if (!rc)
-        rc = r->hashlen == 32 ? tg::launch_install<tg::Sha256>(k, p, *r, s)
-                              : tg::launch_install<tg::Sha384>(k, p, *r, s);
-    if (rc) return fail(rc, "TLS 1.2 install launch failed");
-    rc = sc.release();
-    return rc ? fail(rc, "scratch release failed") : TG_OK;
+    const char* msg = "TLS 1.2 install launch failed";
+    return tg::install_templates(r, s, msg, [&](const uint32_t* tmpl, const tg::PrfGeom& g) {
+        return r->hashlen == 32 ? tg::launch_install<tg::Sha256>(k, tmpl, g, *r, s)
+                                : tg::launch_install<tg::Sha384>(k, tmpl, g, *r, s);
+    });
 }
 
 int tg_cbc_sessions_install_tls12(tg_cbc_key* k, const tg_tls12_install* r, void* stream) {
@@ -554,24 +408,16 @@ int tg_cbc_sessions_install_tls12(tg_cbc_key* k, const tg_tls12_install* r, void
     if (r->n == 0) return TG_OK;
     if (int rc = tg::cbc_select_device(k)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    tg::Scratch sc(s);
-    tg::PrfPack p;
-    int rc = tg::pack_templates((int)r->hashlen, tg::kKeyExpansion, 13, r->server_random, 32, r->client_random, 32,
-                                r->n, sc, &p, s);
-    if (!rc) {
+    const char* msg = "TLS 1.2 CBC install launch failed";
+    return tg::install_templates(r, s, msg, [&](const uint32_t* tmpl, const tg::PrfGeom& g) {
         using namespace tg;
-        if (r->hashlen == 48)
-            rc = launch_cbc_install<Sha384, 8, Sha384>(k, p, *r, s);
-        else if (k->mac == TG_MAC_SHA1)
-            rc = k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha1>(k, p, *r, s)
-                                 : launch_cbc_install<Sha256, 8, Sha1>(k, p, *r, s);
-        else
-            rc = k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha256>(k, p, *r, s)
-                                 : launch_cbc_install<Sha256, 8, Sha256>(k, p, *r, s);
-    }
-    if (rc) return fail(rc, "TLS 1.2 CBC install launch failed");
-    rc = sc.release();
-    return rc ? fail(rc, "scratch release failed") : TG_OK;
+        if (r->hashlen == 48) return launch_cbc_install<Sha384, 8, Sha384>(k, tmpl, g, *r, s);
+        if (k->mac == TG_MAC_SHA1)
+            return k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha1>(k, tmpl, g, *r, s)
+                                   : launch_cbc_install<Sha256, 8, Sha1>(k, tmpl, g, *r, s);
+        return k->rounds == 10 ? launch_cbc_install<Sha256, 4, Sha256>(k, tmpl, g, *r, s)
+                               : launch_cbc_install<Sha256, 8, Sha256>(k, tmpl, g, *r, s);
+    });
 }
 
 }  // extern "C"

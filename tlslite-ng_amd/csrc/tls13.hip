@@ -22,7 +22,7 @@
 // for every session and come as kernel arguments: the HkdfLabel bytes in front
 // of the context as LabelPre, a whole shared message (the "derived" and
 // "finished" labels) as the HkdfMsg that hkdf_kernel takes.  Secrets enter as
-// the two HMAC midstates (prf_dev.h), computed once per lane; every secret
+// the two HMAC midstates (keysetup_dev.h), computed once per lane; every secret
 // between a stage's input and its outputs stays in registers.  Every loop's
 // trip count and every branch on a message position depend on lengths alone,
 // and nothing is held in an array indexed at run time: no kernel here has a
@@ -41,36 +41,11 @@ struct LabelPre {
     uint32_t len;
 };
 
-// Row ``row`` (H::kHash bytes, any alignment; NULL: zeros) as an HMAC key.
-template <class H>
-__device__ __forceinline__ void row_key(const uint8_t* row, typename H::word key[16]) {
-    using W = typename H::word;
-    constexpr int WB = sizeof(W);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k * WB >= H::kHash || !row) {
-            key[k] = W(0);
-        } else if constexpr (WB == 4) {
-            key[k] = bswap32(load_u32u(row + 4 * k));
-        } else {
-            key[k] = ((uint64_t)bswap32(load_u32u(row + 8 * k)) << 32) | bswap32(load_u32u(row + 8 * k + 4));
-        }
-    }
-}
-
 // A digest as an HMAC key.
 template <class H>
 __device__ __forceinline__ void digest_key(const typename H::word st[8], typename H::word key[16]) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) key[k] = k < H::kStateOut ? st[k] : typename H::word(0);
-}
-
-template <class H>
-__device__ __forceinline__ void store_digest(const typename H::word st[8], uint8_t* to) {
-    uint32_t d[12];
-    digest_words<H>(st, d);
-#pragma unroll
-    for (int k = 0; k < H::kHash / 4; ++k) store_u32u(to + 4 * k, bswap32(d[k]));
 }
 
 // st = HMAC under h of   pre || row[0, len) || (COUNTER ? 0x01 : nothing),
@@ -126,7 +101,7 @@ __global__ __launch_bounds__(256) void tls13_extract_kernel(const uint8_t* __res
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     W key[16], st[8];
-    row_key<H>(salts ? salts + (uint64_t)H::kHash * i : nullptr, key);
+    key_from_row<H, H::kHash, true>(salts ? salts + (uint64_t)H::kHash * i : nullptr, key);
     Hm<H> h;
     hm_key<H>(key, h);
     const LabelPre none{};
@@ -141,18 +116,14 @@ __global__ __launch_bounds__(256) void tls13_expand_rows_kernel(LabelPre pre, co
                                                                 uint32_t ctxlen, uint64_t n, uint32_t outlen,
                                                                 uint8_t* __restrict__ out) {
     using W = typename H::word;
-    constexpr int WB = sizeof(W);
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     W key[16], st[8];
-    row_key<H>(secrets + (uint64_t)H::kHash * i, key);
+    key_from_row<H, H::kHash>(secrets + (uint64_t)H::kHash * i, key);
     Hm<H> h;
     hm_key<H>(key, h);
     hm_row<H, true>(h, pre, contexts ? contexts + (uint64_t)ctxlen * i : nullptr, ctxlen, st);
-    const gptr op = (gptr)(out + (uint64_t)outlen * i);
-#pragma unroll
-    for (int k = 0; k < H::kHash; ++k)
-        if ((uint32_t)k < outlen) op[k] = (uint8_t)(st[k / WB] >> (8 * (WB - 1 - (k % WB))));
+    store_digest_bytes<H>(st, out + (uint64_t)outlen * i, outlen);
 }
 
 // ---- tg_tls13_finished -----------------------------------------------------------
@@ -165,7 +136,7 @@ __global__ __launch_bounds__(256) void tls13_finished_kernel(tg::HkdfMsg fin, co
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     W key[16], st[8];
-    row_key<H>(secrets + (uint64_t)H::kHash * i, key);
+    key_from_row<H, H::kHash>(secrets + (uint64_t)H::kHash * i, key);
     hkdf_t1<H>(fin, key, st);
     digest_key<H>(st, key);
     Hm<H> h;
@@ -192,7 +163,7 @@ __global__ __launch_bounds__(256) void tls13_handshake_kernel(tg::HkdfMsg derive
     const LabelPre none{};
     W key[16], st[8], hs[8];
     Hm<H> h;
-    row_key<H>(nullptr, key);                                   // early = Extract(0, psk or zeros)
+    key_from_row<H, H::kHash, true>(nullptr, key);                                   // early = Extract(0, psk or zeros)
     hm_key<H>(key, h);
     hm_row<H, false>(h, none, psk ? psk + (uint64_t)H::kHash * i : nullptr, H::kHash, st);
     digest_key<H>(st, key);                                     // Derive-Secret(early, "derived", Hash(""))
@@ -231,7 +202,7 @@ __global__ __launch_bounds__(256) void tls13_application_kernel(tg::HkdfMsg deri
     const LabelPre none{};
     W key[16], st[8], ms[8], oc[8], os[8], oe[8];
     Hm<H> h;
-    row_key<H>(hs_in + (uint64_t)H::kHash * i, key);            // Derive-Secret(hs, "derived", Hash(""))
+    key_from_row<H, H::kHash>(hs_in + (uint64_t)H::kHash * i, key);            // Derive-Secret(hs, "derived", Hash(""))
     hkdf_t1<H>(derived, key, st);
     digest_key<H>(st, key);                                     // master = Extract(derived, zeros)
     hm_key<H>(key, h);
@@ -274,7 +245,7 @@ LabelPre label_pre(const char* label, int hashlen) {
 
 // Hash(""), derive_secret's transcript for handshake_hashes None.
 template <class H>
-void empty_hash(uint8_t out[48]) {
+void empty_hash_of(uint8_t out[48]) {
     using W = typename H::word;
     W st[8], blk[16] = {0};
     blk[0] = (W)1 << (8 * sizeof(W) - 1);
@@ -284,11 +255,15 @@ void empty_hash(uint8_t out[48]) {
         out[k] = (uint8_t)(st[k / sizeof(W)] >> (8 * (sizeof(W) - 1 - k % sizeof(W))));
 }
 
+void empty_hash(int hashlen, uint8_t out[48]) {
+    if (hashlen == 32) empty_hash_of<Sha256>(out);
+    else empty_hash_of<Sha384>(out);
+}
+
 // HkdfLabel(label, Hash(""), hashlen) or, with ctx false, HkdfLabel(label, "", hashlen).
 int shared_message(int hashlen, const char* label, bool ctx, HkdfMsg* msg) {
     uint8_t eh[48];
-    if (hashlen == 32) empty_hash<Sha256>(eh);
-    else empty_hash<Sha384>(eh);
+    empty_hash(hashlen, eh);
     return host::hkdf_message(hashlen, (const uint8_t*)label, strlen(label), ctx ? eh : nullptr,
                               ctx ? (size_t)hashlen : 0, (size_t)hashlen, msg);
 }
@@ -348,8 +323,7 @@ int tg_hkdf_expand_label_rows(int hashlen, const uint8_t* secrets, uint64_t n, c
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!contexts && ctxlen) {   // Hash(""): one context for all rows, hkdf_kernel's case
         uint8_t eh[48];
-        if (hashlen == 32) empty_hash<Sha256>(eh);
-        else empty_hash<Sha384>(eh);
+        empty_hash(hashlen, eh);
         HkdfMsg msg;
         if (host::hkdf_message(hashlen, label, labellen, eh, ctxlen, outlen, &msg))
             return fail(TG_EINVAL, "label + context too long");
